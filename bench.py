@@ -3,6 +3,13 @@
 bench.py — walker-logL evals/s on Pantheon+-shaped full-covariance chi^2 (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--walkers-per-gpu n] [--scaling weak|strong] [--n-sn 1701]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, preconditions the device and runs the W warm-up steps, times exactly K steps and prints the line
+(`metric`, `value`, `unit`, `ms_per_step`, ...).  `--full` adds what is measured or checked beside the headline: the
+from-idle pass, per-kernel times and the roofline (from a kernel-timing pass of their own), the all-gather alone, device
+identities, the host-visible rate, the HBM triad and the CPU baseline with its GPU-vs-CPU parity.  `--dump-outputs DIR`
+writes the per-walker values of the last timed step (DIR/log_prob.npy, or log_like.npy for a log L workload; float64).
 
 `python bench.py --gpus N` with N > 1 starts the N ranks itself (torch.distributed.run, one process per GPU, RCCL) from
 a parent that never touches a GPU; the driver's own launch
@@ -36,6 +43,23 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X FP64 matrix (= vector) datasheet peak: 256 CU x 4 SIMD x 2048 flop / 64 clk x 2.4 GHz
+
+OUTPUT_NAMES = {0: "chi2", 1: "log_like", 2: "log_prob"}  # CF_OUT_* kinds: the per-walker quantity the timed path returns
+DUMP_MAX_BYTES = 60 << 20  # --dump-outputs writes at most this much data (64 MB with room for the .npy headers)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float64.  Above DUMP_MAX_BYTES in all, every array keeps the same share of
+    its rows, chosen by a fixed seed (sorted row indices), so that two builds given the same arguments dump the same rows."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, len(a) * DUMP_MAX_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
 
 def flops_per_eval_solve(n):
     """Algorithmic FP64 flops of the chi^2 phase per walker: TRSV n(n-1) + n divisions + 2n norm."""
@@ -111,7 +135,17 @@ def main():
                          "(N=1820 SN + 14 BAO + Planck/ACT CMB, physical-density E(z)); desi_des5y_bbn_theta_star = "
                          "configs[4] shape (N=1820 SN + 13 BAO + l_A + BBN prior, thawing dark energy, log P as nautilus "
                          "would batch it); both on the committed fixture data")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the from-idle pass, per-kernel times and the "
+                         "roofline (a kernel-timing pass of their own), the host-visible rate, the all-gather alone, device "
+                         "identities, the HBM triad and the CPU baseline with its parity.  Off: set up, warm up, time the K "
+                         "steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the per-walker values a caller of "
+                         "the timed path receives, all ranks) as DIR/<name>.npy in float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.mode == "inprocess":
         return run_inprocess(args)
@@ -245,30 +279,23 @@ def main():
         fence()
         return time.perf_counter() - t0
 
-    # Two passes of the same W + K protocol.  FROM IDLE: the GPU has done nothing but set-up copies so far and its clock is
-    # still ramping (reported as `from_idle`, never as `value`).  Then `--precondition-ms` of the same evaluations, untimed,
-    # and the pass that counts: the sustained clock, which is what a sampler running for hours sees.
+    # The pass that counts runs at the sustained clock, which is what a sampler running for hours sees: `--precondition-ms` of
+    # the same evaluations, untimed, before its W + K steps.  With --full the same W + K protocol runs once more FIRST, on a GPU
+    # that has done nothing but set-up copies so far and whose clock is still ramping (reported as `from_idle`, never as `value`).
     n_pre, dt_idle = 0, None
-    if args.precondition_ms > 0:
+    if args.full and args.precondition_ms > 0:
         dt_idle = timed_pass()
+    if args.precondition_ms > 0:
         t_pre = time.perf_counter()
         while (time.perf_counter() - t_pre) * 1e3 < args.precondition_ms:
             for _ in range(16):
                 eng.eval_device(theta_local.data_ptr(), Wl, logp.data_ptr(), kind, stream)
             torch.cuda.synchronize()
             n_pre += 16
-    # kernel durations from HIP events on the stream the kernels run on, SAMPLED over the timed region: recording them on
-    # every step costs 5 % of the step (profiles/r02_event_overhead.txt); the first warm-up step is sampled too and dropped
-    stride = max(1, min(8, args.steps // 5))
-    eng.enable_timing(min(args.steps + args.warmup, 4096), stride)
     dt = timed_pass()
-    kms = eng.kernel_ms3()
-    n_warm_samples = (args.warmup + stride - 1) // stride  # samples that fell into the W warm-up steps
-    kms = kms[n_warm_samples:] or kms
-    eng.enable_timing(0)
-    dt_by_rank, allgather_ms = [dt], None
+    dt_by_rank = [dt]
     if use_dist:
-        # every rank's own clock around the K steps (value uses the MAX), and the exchange alone: K all-gathers with nothing else
+        # every rank's own clock around the K steps (value uses the MAX)
         own = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         per_rank = [torch.zeros_like(own) for _ in range(world)]
         dist.all_gather(per_rank, own)
@@ -276,42 +303,62 @@ def main():
         t = torch.tensor([dt, dt_idle or 0.0], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, dt_idle = float(t[0].item()), (float(t[1].item()) if dt_idle is not None else None)
-        got = theta_all.cpu().numpy()
-        assert np.array_equal(got, theta_all_host), "all-gather of walker positions is wrong"
-        if backend == "nccl":
-            fence()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                dist.all_gather_into_tensor(theta_all, theta_local)
-            fence()
-            ag = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-            dist.all_reduce(ag, op=dist.ReduceOp.MAX)
-            allgather_ms = float(ag.item()) / args.steps * 1e3
+    result = logp.cpu().numpy() if (args.full or args.dump_outputs) else None  # the last timed step's values, this rank's walkers
+    if args.dump_outputs:
+        every = result
+        if use_dist:
+            if backend == "nccl":
+                every = torch.empty(W_total, dtype=torch.float64, device=dev)
+                dist.all_gather_into_tensor(every, logp)
+            else:  # rehearsal backend without device collectives: through the host
+                every = torch.empty(W_total, dtype=torch.float64)
+                dist.all_gather_into_tensor(every, torch.from_numpy(result))
+            every = every.cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {OUTPUT_NAMES[int(kind)]: every})
 
-    result = logp.cpu().numpy()
-    assert np.all(np.isfinite(result)), "in-box walkers must give a finite log-probability"
+    kms, stride, allgather_ms, idents = None, None, None, None
+    if args.full:
+        # kernel durations from HIP events on the stream the kernels run on, SAMPLED over a W + K pass of their own after the
+        # timed one: recording them on every step costs 5 % of the step (profiles/r02_event_overhead.txt); the first warm-up
+        # step is sampled too and dropped
+        stride = max(1, min(8, args.steps // 5))
+        eng.enable_timing(min(args.steps + args.warmup, 4096), stride)
+        timed_pass()
+        kms = eng.kernel_ms3()
+        n_warm_samples = (args.warmup + stride - 1) // stride  # samples that fell into the W warm-up steps
+        kms = kms[n_warm_samples:] or kms
+        eng.enable_timing(0)
+        if use_dist:
+            # the exchange alone: K all-gathers with nothing else
+            got = theta_all.cpu().numpy()
+            assert np.array_equal(got, theta_all_host), "all-gather of walker positions is wrong"
+            if backend == "nccl":
+                fence()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    dist.all_gather_into_tensor(theta_all, theta_local)
+                fence()
+                ag = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
+                dist.all_reduce(ag, op=dist.ReduceOp.MAX)
+                allgather_ms = float(ag.item()) / args.steps * 1e3
 
-    # which physical device each rank ran on (uuid / PCI address), gathered so that rank 0 can show they are distinct
-    props = torch.cuda.get_device_properties(dev)
-    ident = "%s pci %04x:%02x:%02x uuid %s" % (props.name, getattr(props, "pci_domain_id", 0), getattr(props, "pci_bus_id", 0),
-                                              getattr(props, "pci_device_id", 0), getattr(props, "uuid", "?"))
-    idents = [ident]
-    if use_dist:
-        idents = [None] * world
-        dist.all_gather_object(idents, ident)
+        assert np.all(np.isfinite(result)), "in-box walkers must give a finite log-probability"
+
+        # which physical device each rank ran on (uuid / PCI address), gathered so that rank 0 can show they are distinct
+        props = torch.cuda.get_device_properties(dev)
+        ident = "%s pci %04x:%02x:%02x uuid %s" % (props.name, getattr(props, "pci_domain_id", 0), getattr(props, "pci_bus_id", 0),
+                                                  getattr(props, "pci_device_id", 0), getattr(props, "uuid", "?"))
+        idents = [ident]
+        if use_dist:
+            idents = [None] * world
+            dist.all_gather_object(idents, ident)
 
     if rank == 0:
-        solve_kernel = "tri_gemm_chi2_kernel" if eng.info()["solve_mode"] == pkg.CF_SOLVE_INVERSE_GEMM else "trsm_chi2_kernel"
-        walker_ms = float(np.mean([k[0] for k in kms]))
-        blocks_ms = float(np.mean([k[1] for k in kms]))
-        solve_ms = float(np.mean([k[2] for k in kms]))
-        solve_flops = flops_per_eval_solve(args.n_sn) * Wl
-        achieved = solve_flops / (solve_ms * 1e-3) / 1e12
-        traffic, traffic_source = pmc_traffic(args.workload if args.fde == "lcdm" else f"{args.workload}:{args.fde}", args.n_sn, Wl,
-                                              solve_kernel)
         out = {
             # `value`: theta already resident in HBM when the timed region starts (the bench contract); the same metric as
             # SURVEY 8(d) words it -- host buffers in and out, PCIe and the synchronisation included -- is `value_host_visible`
+            # (--full)
             "metric": {"pantheon": "walker-logL evals/s, Pantheon+ 1701-SN full-cov chi2, theta resident in HBM",
                        "desi_cmb_des5y": "walker-logL evals/s, DESI BAO + Planck/ACT CMB + DES-SN joint chi2 (config 3 shape), theta resident in HBM",
                        "desi_des5y_bbn_theta_star": "walker-logL evals/s, DESI BAO + l_A + BBN + DES-SN joint log P (config 5 shape), theta resident in HBM",
@@ -323,7 +370,6 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3,
             "ms_per_step_by_rank": [x / args.steps * 1e3 for x in dt_by_rank],
-            "allgather_ms_per_step": allgather_ms,  # K all-gathers of the positions alone, max over ranks (None: no RCCL in this run)
             "mode": "ranks",
             "higher_is_better": True,
             "scaling": args.scaling,
@@ -348,78 +394,100 @@ def main():
             },
             "backend": ("rccl (torch.distributed nccl)" if backend == "nccl" else backend) if use_dist else None,
             "world_size": world,
-            "device_ids": idents,
-            "distinct_devices": len(set(idents)),
-            "roofline": {
-                "kernel": solve_kernel,
-                "bound": "mfma",
-                "achieved": achieved,
-                "peak": FP64_MFMA_PEAK_TFLOPS,
-                "unit": "TFLOP/s",
-                "frac": achieved / FP64_MFMA_PEAK_TFLOPS,
-                "traffic": traffic,
-                "traffic_source": traffic_source,
-                "flops_per_launch": solve_flops,
-                "avg_kernel_ms": solve_ms,
-            },
-            "kernels_ms": {"walker_kernel": walker_ms, "small_blocks_kernel": blocks_ms if (args.workload != "pantheon") else None,
-                           solve_kernel: solve_ms},
-            "kernel_timing": f"HIP events on the launch stream, every {stride}th of the {args.steps} timed steps ({len(kms)} samples); a "
-                             "sampled step pays for its four event records (profiles/r02_event_overhead.txt), so kernels_ms overstate the "
-                             "untimed steps' kernels by 0.5-2.5 % and may sum to more than ms_per_step; roofline.frac is that much conservative",
             "preconditioning": {"untimed_evaluations_before_warmup": n_pre, "ms": args.precondition_ms},
-            "from_idle": None if dt_idle is None else {
-                "value": W_total * args.steps / dt_idle, "ms_per_step": dt_idle / args.steps * 1e3,
-                "note": "the same W warm-up + K timed steps run FIRST, on a GPU straight from idle (clock still ramping); "
-                        "`value` is the second pass, after the preconditioning"},
             "device": {k: eng.info()[k] for k in ("gcn_arch", "cu_count")},
         }
-        # the HBM view next to the matrix-core view.  `hbm_gbps_measured` = PMC bytes of the solve
-        # kernel / its duration (small by design: the factor is reused by every walker from L2 / Infinity Cache);
-        # `trsv_equivalent_gbps` = what a design without reuse would have to stream (8 N (N+1) / 2 bytes per eval),
-        # quoted for comparison with the CPU path only -- it exceeds the 8 TB/s HBM peak because of the reuse.
-        if solve_kernel == "tri_gemm_chi2_kernel":
-            # frac = mfma_busy x useful / executed x clock / 2.4 GHz: the matrix instructions the launch EXECUTES are arithmetic
-            # (diagonal blocks and padded rows in full), their 64 cycles each on 1024 SIMDs against the kernel's duration at the
-            # clock the chip holds under it (in-kernel s_memtime / s_memrealtime of the diagnostic build, replayed from profiles/)
-            n_mfma = executed_mfmas_solve(args.n_sn, Wl)
-            clock_ghz, clock_source, bare = replay_clock()
-            r = out["roofline"]
-            r["executed_tflops"] = n_mfma * 2048 / (solve_ms * 1e-3) / 1e12
-            r["useful_over_executed"] = solve_flops / (n_mfma * 2048.0)
-            r["clock_ghz"], r["clock_source"] = clock_ghz, clock_source
-            r["mfma_busy"] = n_mfma * 64 / 1024.0 / (solve_ms * 1e-3 * clock_ghz * 1e9) if clock_ghz else None
-            r["frac_factors"] = None if not clock_ghz else {"mfma_busy": r["mfma_busy"], "useful_over_executed": r["useful_over_executed"],
-                                                            "clock_over_2p4": clock_ghz / 2.4}
-            r["bare_mfma_loop_tflops"] = bare  # what a register-only v_mfma_f64_16x16x4_f64 loop sustains on this silicon (same source)
-        out["roofline"]["hbm_gbps_measured"] = traffic / (solve_ms * 1e-3) / 1e9 if traffic else None
-        out["roofline"]["trsv_equivalent_gbps"] = 8.0 * args.n_sn * (args.n_sn + 1) / 2 * out["value"] / 1e9
-        if world == 1 and not args.no_cpu_baseline:  # context probes (this and cpu_baseline) stay out of profiled runs
-            out["roofline"]["hbm_stream_triad_gbps"] = stream_triad_gbps(torch, dev)
-        if world == 1 and args.workload == "pantheon":
-            # the ctypes boundary as emcee / nautilus call it: host numpy in, host numpy out (PCIe + sync included).
-            # Reported for DESIGN.md; never the headline `value`.
-            th_host = theta_all_host[mine]
-            for _ in range(3):
-                lk.log_probs_vectorized(th_host)
-            t0 = time.perf_counter()
-            reps = max(50, args.steps)  # ~15 ms: a handful of calls is at the mercy of one scheduling hiccup
-            for _ in range(reps):
-                host_res = lk.log_probs_vectorized(th_host)
-            # SURVEY 8(d)'s own wording of the metric: wall-clock, host-visible, H2D of theta and D2H of the results
-            # included -- first-class beside `value` (which is theta-resident, as the bench contract asks)
-            out["value_host_visible"] = Wl * reps / (time.perf_counter() - t0)
-            out["host_visible"] = {"metric": "walker-logL evals/s, Pantheon+ 1701-SN full-cov chi2, host numpy buffers through cf_eval "
-                                             "(H2D + kernels + D2H + sync: SURVEY 8d's wording of the metric)",
-                                   "value": out["value_host_visible"], "unit": "evals/s", "calls": reps}
-            assert np.array_equal(host_res, result)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(pkg, args, syn, lk, box, kind, theta_all_host, result, args.cpu_seconds)
+        if args.full:
+            report_full(out, args, pkg, torch, dev, lk, syn, box, kind, world, Wl, W_total, theta_all_host, mine, result, kms,
+                        stride, allgather_ms, idents, dt_idle)
         print(json.dumps(out), flush=True)
 
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def report_full(out, args, pkg, torch, dev, lk, syn, box, kind, world, Wl, W_total, theta_all_host, mine, result, kms, stride,
+                allgather_ms, idents, dt_idle):
+    """The --full figures beside the headline, added to rank 0's line `out`: per-kernel times and the roofline, from_idle, the
+    device identities, the all-gather alone, the host-visible rate, the HBM triad and the CPU baseline with its parity."""
+    eng = lk.engine
+    solve_kernel = "tri_gemm_chi2_kernel" if eng.info()["solve_mode"] == pkg.CF_SOLVE_INVERSE_GEMM else "trsm_chi2_kernel"
+    walker_ms = float(np.mean([k[0] for k in kms]))
+    blocks_ms = float(np.mean([k[1] for k in kms]))
+    solve_ms = float(np.mean([k[2] for k in kms]))
+    solve_flops = flops_per_eval_solve(args.n_sn) * Wl
+    achieved = solve_flops / (solve_ms * 1e-3) / 1e12
+    traffic, traffic_source = pmc_traffic(args.workload if args.fde == "lcdm" else f"{args.workload}:{args.fde}", args.n_sn, Wl,
+                                          solve_kernel)
+    out.update({
+        "allgather_ms_per_step": allgather_ms,  # K all-gathers of the positions alone, max over ranks (None: no RCCL in this run)
+        "device_ids": idents,
+        "distinct_devices": len(set(idents)),
+        "roofline": {
+            "kernel": solve_kernel,
+            "bound": "mfma",
+            "achieved": achieved,
+            "peak": FP64_MFMA_PEAK_TFLOPS,
+            "unit": "TFLOP/s",
+            "frac": achieved / FP64_MFMA_PEAK_TFLOPS,
+            "traffic": traffic,
+            "traffic_source": traffic_source,
+            "flops_per_launch": solve_flops,
+            "avg_kernel_ms": solve_ms,
+        },
+        "kernels_ms": {"walker_kernel": walker_ms, "small_blocks_kernel": blocks_ms if (args.workload != "pantheon") else None,
+                       solve_kernel: solve_ms},
+        "kernel_timing": f"HIP events on the launch stream, every {stride}th of {args.steps} steps ({len(kms)} samples) of a W + K pass "
+                         "of their own after the timed one; a sampled step pays for its four event records "
+                         "(profiles/r02_event_overhead.txt), so kernels_ms overstate the unsampled steps' kernels by 0.5-2.5 % and may sum "
+                         "to more than ms_per_step; roofline.frac is that much conservative",
+        "from_idle": None if dt_idle is None else {
+            "value": W_total * args.steps / dt_idle, "ms_per_step": dt_idle / args.steps * 1e3,
+            "note": "the same W warm-up + K timed steps run FIRST, on a GPU straight from idle (clock still ramping); "
+                    "`value` is the second pass, after the preconditioning"},
+    })
+    # SURVEY 8(d): the HBM view next to the matrix-core view.  `hbm_gbps_measured` = PMC bytes of the solve
+    # kernel / its duration (small by design: the factor is reused by every walker from L2 / Infinity Cache);
+    # `trsv_equivalent_gbps` = what a design without reuse would have to stream (8 N (N+1) / 2 bytes per eval),
+    # quoted for comparison with the CPU path only -- it exceeds the 8 TB/s HBM peak because of the reuse.
+    if solve_kernel == "tri_gemm_chi2_kernel":
+        # frac = mfma_busy x useful / executed x clock / 2.4 GHz: the matrix instructions the launch EXECUTES are arithmetic
+        # (diagonal blocks and padded rows in full), their 64 cycles each on 1024 SIMDs against the kernel's duration at the
+        # clock the chip holds under it (in-kernel s_memtime / s_memrealtime of the diagnostic build, replayed from profiles/)
+        n_mfma = executed_mfmas_solve(args.n_sn, Wl)
+        clock_ghz, clock_source, bare = replay_clock()
+        r = out["roofline"]
+        r["executed_tflops"] = n_mfma * 2048 / (solve_ms * 1e-3) / 1e12
+        r["useful_over_executed"] = solve_flops / (n_mfma * 2048.0)
+        r["clock_ghz"], r["clock_source"] = clock_ghz, clock_source
+        r["mfma_busy"] = n_mfma * 64 / 1024.0 / (solve_ms * 1e-3 * clock_ghz * 1e9) if clock_ghz else None
+        r["frac_factors"] = None if not clock_ghz else {"mfma_busy": r["mfma_busy"], "useful_over_executed": r["useful_over_executed"],
+                                                        "clock_over_2p4": clock_ghz / 2.4}
+        r["bare_mfma_loop_tflops"] = bare  # what a register-only v_mfma_f64_16x16x4_f64 loop sustains on this silicon (same source)
+    out["roofline"]["hbm_gbps_measured"] = traffic / (solve_ms * 1e-3) / 1e9 if traffic else None
+    out["roofline"]["trsv_equivalent_gbps"] = 8.0 * args.n_sn * (args.n_sn + 1) / 2 * out["value"] / 1e9
+    if world == 1 and not args.no_cpu_baseline:  # context probes (this and cpu_baseline) stay out of profiled runs
+        out["roofline"]["hbm_stream_triad_gbps"] = stream_triad_gbps(torch, dev)
+    if world == 1 and args.workload == "pantheon":
+        # the ctypes boundary as emcee / nautilus call it: host numpy in, host numpy out (PCIe + sync included).
+        # Reported for DESIGN.md; never the headline `value`.
+        th_host = theta_all_host[mine]
+        for _ in range(3):
+            lk.log_probs_vectorized(th_host)
+        t0 = time.perf_counter()
+        reps = max(50, args.steps)  # ~15 ms: a handful of calls is at the mercy of one scheduling hiccup
+        for _ in range(reps):
+            host_res = lk.log_probs_vectorized(th_host)
+        # SURVEY 8(d)'s own wording of the metric: wall-clock, host-visible, H2D of theta and D2H of the results
+        # included -- first-class beside `value` (which is theta-resident, as the bench contract asks)
+        out["value_host_visible"] = Wl * reps / (time.perf_counter() - t0)
+        out["host_visible"] = {"metric": "walker-logL evals/s, Pantheon+ 1701-SN full-cov chi2, host numpy buffers through cf_eval "
+                                         "(H2D + kernels + D2H + sync: SURVEY 8d's wording of the metric)",
+                               "value": out["value_host_visible"], "unit": "evals/s", "calls": reps}
+        assert np.array_equal(host_res, result)
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(pkg, args, syn, lk, box, kind, theta_all_host, result, args.cpu_seconds)
 
 
 def stream_triad_gbps(torch, dev, n=1 << 27, reps=10):
@@ -498,9 +566,13 @@ def run_inprocess(args):
     for _ in range(args.steps):
         res = lk.log_probs_vectorized(theta)
     dt, cpu = time.perf_counter() - t0, time.process_time() - cpu0
-    assert np.all(np.isfinite(res))
-    one = sn.PantheonLikelihood(syn["z_cmb"], syn["z_hel"], syn["obs"], chol=syn["chol"], device=devs[0])
-    assert np.array_equal(one.log_probs_vectorized(theta[:4096]), res[:4096]), "replicas changed a walker's result"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"log_prob": res})
+    if args.full:
+        assert np.all(np.isfinite(res))
+        one = sn.PantheonLikelihood(syn["z_cmb"], syn["z_hel"], syn["obs"], chol=syn["chol"], device=devs[0])
+        assert np.array_equal(one.log_probs_vectorized(theta[:4096]), res[:4096]), "replicas changed a walker's result"
+        one.engine.close()
     solve_flops = flops_per_eval_solve(args.n_sn) * W
     idents = []
     for d in sorted(set(devs)):
@@ -527,7 +599,6 @@ def run_inprocess(args):
     }
     print(json.dumps(out), flush=True)
     lk.engine.close()
-    one.engine.close()
 
 
 def pmc_traffic(workload, n_sn, walkers, kernel):

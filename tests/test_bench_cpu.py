@@ -45,6 +45,29 @@ def test_strong_scaling_needs_whole_panels_per_rank():
     assert r.returncode == 0 and "--scaling" in r.stdout and "--walkers-total" in r.stdout and "--fde" in r.stdout
 
 
+def test_full_and_dump_outputs_options_and_at_least_one_timed_step():
+    r = _run(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr and "{" not in r.stdout
+
+
+def test_dump_outputs_writes_float64_and_samples_a_large_output_with_a_fixed_seed(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+
+    x = np.arange(1000, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"log_prob": x.astype(np.float32)})
+    got = np.load(tmp_path / "a" / "log_prob.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, x)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 800)  # 100 of the 1000 rows
+    bench.dump_outputs(str(tmp_path / "b"), {"log_prob": x})
+    bench.dump_outputs(str(tmp_path / "c"), {"log_prob": x})
+    b, c = np.load(tmp_path / "b" / "log_prob.npy"), np.load(tmp_path / "c" / "log_prob.npy")
+    assert b.size == 100 and np.array_equal(b, c) and np.all(np.diff(b) > 0) and b[-1] < 1000
+
+
 def test_one_per_gpu_shape_at_every_world_size_and_the_inprocess_arguments():
     """the weak-scaling default keeps 4096 walkers per GPU at N = 1, 2, 4 AND 8 (round 3 switched to 8192 at
     N = 8 under the same label); configs[3] (65536 walkers over 8 GPUs) is `--scaling strong`; `--mode inprocess` is one process over

@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -25,7 +26,7 @@ def test_bench_under_torchrun_runs_rccl_with_one_rank(pkg):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
-           "--no-cpu-baseline", "--precondition-ms", "0", "--walkers-per-gpu", "1024", "--n-sn", "300"]
+           "--no-cpu-baseline", "--precondition-ms", "0", "--walkers-per-gpu", "1024", "--n-sn", "300", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -40,10 +41,10 @@ def test_bench_under_torchrun_runs_rccl_with_one_rank(pkg):
     assert d["config"]["walkers_per_gpu"] == 1024 and d["scaling"] == "weak"
 
 
-def test_bench_two_ranks_rehearsed_over_gloo_on_one_gpu(pkg):
+def test_bench_two_ranks_rehearsed_over_gloo_on_one_gpu(pkg, tmp_path):
     """The N = 2 code path of bench.py (sharding of the walkers, per-rank times gathered, max over ranks) with two rank PROCESSES
     sharing the box's one GPU: RCCL refuses that, so the rehearsal backend stages the all-gather through the host (labelled in the
-    line).  What this cannot show is inter-GPU transport."""
+    line).  What this cannot show is inter-GPU transport.  `--dump-outputs` gathers both ranks' values in walker order."""
     if pkg.lib().cf_device_count() < 1:
         pytest.fail("GPU tests need an MI355X; no HIP device visible (there is no fallback path)")
     with socket.socket() as so:
@@ -53,7 +54,8 @@ def test_bench_two_ranks_rehearsed_over_gloo_on_one_gpu(pkg):
     env["BENCH_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--no-cpu-baseline", "--precondition-ms", "0", "--walkers-per-gpu", "512", "--n-sn", "300"]
+           "--no-cpu-baseline", "--precondition-ms", "0", "--walkers-per-gpu", "512", "--n-sn", "300", "--full",
+           "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -63,6 +65,10 @@ def test_bench_two_ranks_rehearsed_over_gloo_on_one_gpu(pkg):
     assert d["config"]["walkers_per_gpu"] == 512 and d["config"]["walkers_total"] == 1024
     assert len(d["ms_per_step_by_rank"]) == 2 and max(d["ms_per_step_by_rank"]) == pytest.approx(d["ms_per_step"], rel=1e-9)
     assert d["allgather_ms_per_step"] is None and d["distinct_devices"] == 1 and len(d["device_ids"]) == 2
+    got = np.load(tmp_path / "log_prob.npy")
+    syn = pkg.synthetic.pantheon_like(n_sn=300, seed=0)
+    lk = pkg.sn_pantheon.PantheonLikelihood(syn["z_cmb"], syn["z_hel"], syn["obs"], chol=syn["chol"])
+    np.testing.assert_allclose(got, lk.log_probs_vectorized(pkg.synthetic.walkers(pkg.sn_pantheon.bounds, 1024, seed=0)), rtol=1e-12)
 
 
 
@@ -74,7 +80,7 @@ def test_bench_inprocess_mode_over_repeated_ordinals(pkg):
         pytest.fail("GPU tests need an MI355X; no HIP device visible (there is no fallback path)")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "inprocess", "--devices", "0,0,0", "--walkers-total", "6144",
-           "--n-sn", "300", "--steps", "3", "--warmup", "1", "--precondition-ms", "0"]
+           "--n-sn", "300", "--steps", "3", "--warmup", "1", "--precondition-ms", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
