@@ -15,10 +15,10 @@ from . import cmb_data, interpolator, laplace, likelihoods, scripts, solve_trian
 
 
 def __getattr__(name):
-    # `ensemble` needs torch; import it lazily so that ctypes-only users do not pay for it
-    if name == "ensemble":
+    # `ensemble` and `chain_stats` need torch; import them lazily so that ctypes-only users do not pay for it
+    if name in ("ensemble", "chain_stats"):
         import importlib
-        return importlib.import_module(__name__ + ".ensemble")
+        return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)
 
 

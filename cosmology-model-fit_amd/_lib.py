@@ -131,6 +131,11 @@ EXPORTS = {
     "cf_ens_propose": (C.c_int, [_I32, _VP, _I64, _I32, _I32, _I32, C.c_uint64, _VP, _I64, C.c_uint64, C.c_double,
                                  C.c_double, _VP, _VP, _VP, _VP, _VP]),
     "cf_ens_accept": (C.c_int, [_VP, _VP, _I64, C.c_int32, C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "cf_ens_accept_record": (C.c_int, [_VP, _VP, _I64, C.c_int32, C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                       _VP]),
+    "cf_chain_mean": (C.c_int, [_VP, _I64, _I64, _VP, _VP]),
+    "cf_chain_lagsum": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _I32, _VP, _VP]),
+    "cf_chain_acf_mean": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "cf_selftest_pack_host": (C.c_int, [_VP, _I64, _I64, _VP, C.POINTER(C.c_double), C.POINTER(_I64)]),
 }
 

@@ -423,11 +423,15 @@ ens_propose_kernel(int kind, const double* __restrict__ all_pos, int64_t nc, int
   }
 }
 
-// accept with probability min(1, exp(log_factor + lp_new - lp_old)); NaN never accepts
+// accept with probability min(1, exp(log_factor + lp_new - lp_old)); NaN never accepts.
+// Recording (cf_ens_accept_record; the pointers are kernel arguments, so the null checks are wave-uniform): the walker's row and
+// log P after the accept go to its local slot of the chain, its accept bit to its counter.  The accept itself is the same code
+// with and without recording.
 extern "C" __global__ void __launch_bounds__(256)
 ens_accept_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ local_idx, int64_t n_active, int ndim, uint64_t key0,
                   const double* __restrict__ y, const double* __restrict__ lp_new, const double* __restrict__ log_factor,
-                  double* __restrict__ x_local, double* __restrict__ logp_local, unsigned long long* __restrict__ n_accepted) {
+                  double* __restrict__ x_local, double* __restrict__ logp_local, unsigned long long* __restrict__ n_accepted,
+                  double* __restrict__ chain_slot, double* __restrict__ logp_slot, long long* __restrict__ walker_accepted) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   bool acc = false;
   if (i < n_active) {
@@ -438,6 +442,11 @@ ens_accept_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ l
       for (int k = 0; k < ndim; ++k) x_local[li * ndim + k] = y[i * ndim + k];
       logp_local[li] = lp_new[i];
     }
+    if (chain_slot) {
+      for (int k = 0; k < ndim; ++k) chain_slot[li * ndim + k] = x_local[li * ndim + k];
+      logp_slot[li] = logp_local[li];
+    }
+    if (walker_accepted) walker_accepted[li] += acc ? 1 : 0;
   }
   const unsigned long long m = __ballot(acc);
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_accepted, (unsigned long long)__popcll(m));
@@ -520,8 +529,24 @@ extern "C" int cf_ens_accept(const int64_t* d_ids, const int64_t* d_local_idx, i
   if (n_active <= 0) return CF_OK;
   hipLaunchKernelGGL(ens_accept_kernel, dim3((unsigned)((n_active + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, d_ids,
                      d_local_idx, n_active, (int)ndim, key0, d_y, d_lp_new, d_log_factor, d_x_local, d_logp_local,
-                     (unsigned long long*)d_n_accepted);
+                     (unsigned long long*)d_n_accepted, (double*)nullptr, (double*)nullptr, (long long*)nullptr);
   return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_ens_accept: launch failed");
+}
+
+extern "C" int cf_ens_accept_record(const int64_t* d_ids, const int64_t* d_local_idx, int64_t n_active, int32_t ndim, uint64_t key0,
+                                    const double* d_y, const double* d_lp_new, const double* d_log_factor, double* d_x_local,
+                                    double* d_logp_local, uint64_t* d_n_accepted, double* d_chain_slot, double* d_logp_slot,
+                                    int64_t* d_walker_accepted, void* hip_stream) {
+  if (ndim < 1 || ndim > CF_ENS_MAX_NDIM) return cf_set_error(CF_ERR_INVALID, "cf_ens_accept_record: ndim must be in 1..16");
+  if (!d_ids || !d_local_idx || !d_y || !d_lp_new || !d_log_factor || !d_x_local || !d_logp_local || !d_n_accepted)
+    return cf_set_error(CF_ERR_INVALID, "cf_ens_accept_record: null argument");
+  if (!d_chain_slot != !d_logp_slot)
+    return cf_set_error(CF_ERR_INVALID, "cf_ens_accept_record: d_chain_slot and d_logp_slot must both be null or both be set");
+  if (n_active <= 0) return CF_OK;
+  hipLaunchKernelGGL(ens_accept_kernel, dim3((unsigned)((n_active + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, d_ids,
+                     d_local_idx, n_active, (int)ndim, key0, d_y, d_lp_new, d_log_factor, d_x_local, d_logp_local,
+                     (unsigned long long*)d_n_accepted, d_chain_slot, d_logp_slot, (long long*)d_walker_accepted);
+  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_ens_accept_record: launch failed");
 }
 
 extern "C" int cf_ens_active_set(uint64_t split_key, int32_t n_splits, int32_t split, int64_t shard_start, int64_t shard_stop,

@@ -144,7 +144,10 @@ class NativeMoves:
         self.ids = torch.empty(nmax, dtype=torch.int64, device=dev)
         self.idx = torch.empty(nmax, dtype=torch.int64, device=dev)
 
-    def split_step(self, e, move, n_splits, split, allpos, split_key):
+    def split_step(self, e, move, n_splits, split, allpos, split_key, record=None):
+        """record: None, or device addresses (chain slot [W_local, ndim] or None, log-P slot [W_local] or None, accept counts
+        [W_local] int64): the accept kernel also writes the walkers' end-of-step rows into the slot and counts their
+        accepts (cf_ens_accept_record, same launch)."""
         L, lib = self.L, self.lib
         kind = _KIND[move]
         stream = torch.cuda.current_stream(e.x.device).cuda_stream
@@ -164,8 +167,14 @@ class NativeMoves:
                                    float(e.a), float(e.de_sigma), self.kde_params.data_ptr(), self.kde_wc.data_ptr(),
                                    y.data_ptr(), logfac.data_ptr(), stream))
         lp_new = e.log_prob_fn(y)
-        L.check(lib.cf_ens_accept(ids.data_ptr(), idx.data_ptr(), n, e.ndim, key0, y.data_ptr(), lp_new.data_ptr(),
-                                  logfac.data_ptr(), e.x.data_ptr(), e.logp.data_ptr(), self.n_acc.data_ptr(), stream))
+        if record is None:
+            L.check(lib.cf_ens_accept(ids.data_ptr(), idx.data_ptr(), n, e.ndim, key0, y.data_ptr(), lp_new.data_ptr(),
+                                      logfac.data_ptr(), e.x.data_ptr(), e.logp.data_ptr(), self.n_acc.data_ptr(), stream))
+        else:
+            slot, lp_slot, counts = record
+            L.check(lib.cf_ens_accept_record(ids.data_ptr(), idx.data_ptr(), n, e.ndim, key0, y.data_ptr(), lp_new.data_ptr(),
+                                             logfac.data_ptr(), e.x.data_ptr(), e.logp.data_ptr(), self.n_acc.data_ptr(),
+                                             slot, lp_slot, counts, stream))
         e._n_proposed += n
 
 
@@ -215,6 +224,12 @@ class ShardedEnsemble:
         # a backend without device collectives (gloo: rank processes sharing one GPU, CPU rehearsals): the all-gather of
         # device-resident positions is staged through the host
         self._host_staged = self.distributed and self.x.is_cuda and "nccl" not in str(dist.get_backend(group)).lower()
+        # the recorded chain (run_mcmc): this rank's walkers only, [capacity, W_local, ndim] / [capacity, W_local]
+        self._chain = torch.empty((0, self.stop - self.start, self.ndim), dtype=self.x.dtype, device=self.x.device)
+        self._chain_logp = torch.empty((0, self.stop - self.start), dtype=self.logp.dtype, device=self.x.device)
+        self._iteration = 0
+        self._walker_acc = torch.zeros(self.stop - self.start, dtype=torch.int64, device=self.x.device)
+        self._mcmc_steps = 0
         if moves_impl is None:
             if not self.x.is_cuda:
                 raise RuntimeError("ShardedEnsemble runs its moves in the library's HIP kernels: the positions must be on an "
@@ -267,11 +282,17 @@ class ShardedEnsemble:
     def step(self):
         """Per split: all-gather -> [KDE fit] -> propose -> log P -> accept; with the library's kernels everything is
         asynchronous on the current stream."""
+        self._step(None)
+
+    def _step(self, record):
         move = self._pick_move()
         n_splits = self.de_splits if move == "de" else 2
         split_key = stream_key(self.seed, self.step_count, 0, _SPLIT_STREAM) if self.randomize_split else 0
         for split in range(n_splits):
-            self.impl.split_step(self, move, n_splits, split, self.gather_positions(), split_key)
+            if record is None:
+                self.impl.split_step(self, move, n_splits, split, self.gather_positions(), split_key)
+            else:
+                self.impl.split_step(self, move, n_splits, split, self.gather_positions(), split_key, record=record)
         self.step_count += 1
 
     @property
@@ -294,6 +315,101 @@ class ShardedEnsemble:
         if self.world > 1:
             dist.all_reduce(acc, group=self.group)
         return float(acc[0] / torch.clamp(acc[1], min=1.0))
+
+    # ---- emcee's results interface: a chain recorded on the device -----------------------------------------------
+    def run_mcmc(self, nsteps: int, thin_by: int = 1):
+        """emcee's ``run_mcmc``: make nsteps * thin_by steps and store every thin_by-th end-of-step state (positions and
+        log P of this rank's walkers) on the device.  With the library's kernels the accept kernel writes the slot and the
+        per-walker accept counts (cf_ens_accept_record): no extra launch and no host sync per step.  Any other
+        ``moves_impl`` (the tensor statement in tests) gets the slot filled by a copy of x / log P after the step."""
+        nsteps, thin_by = int(nsteps), int(thin_by)
+        if nsteps < 0 or thin_by < 1:
+            raise ValueError("run_mcmc needs nsteps >= 0 and thin_by >= 1")
+        need = self._iteration + nsteps
+        if need > self._chain.shape[0]:  # grow once per call
+            chain = torch.empty((need,) + tuple(self._chain.shape[1:]), dtype=self._chain.dtype, device=self._chain.device)
+            logp = torch.empty((need,) + tuple(self._chain_logp.shape[1:]), dtype=self._chain_logp.dtype, device=self._chain.device)
+            chain[: self._iteration] = self._chain[: self._iteration]
+            logp[: self._iteration] = self._chain_logp[: self._iteration]
+            self._chain, self._chain_logp = chain, logp
+        native = isinstance(self.impl, NativeMoves)
+        # slot addresses by arithmetic on the base pointers (no tensor views in the step loop)
+        chain_ptr, logp_ptr, acc_ptr = self._chain.data_ptr(), self._chain_logp.data_ptr(), self._walker_acc.data_ptr()
+        chain_row = self._chain.stride(0) * self._chain.element_size()
+        logp_row = self._chain_logp.stride(0) * self._chain_logp.element_size()
+        for i in range(nsteps * thin_by):
+            store = (i + 1) % thin_by == 0
+            slot = self._iteration
+            if native:
+                self._step((chain_ptr + slot * chain_row, logp_ptr + slot * logp_row, acc_ptr) if store else
+                           (None, None, acc_ptr))
+            else:
+                self._step(None)
+                if store:
+                    self._chain[slot].copy_(self.x)
+                    self._chain_logp[slot].copy_(self.logp)
+            self._mcmc_steps += 1
+            if store:
+                self._iteration += 1
+        return self
+
+    @property
+    def iteration(self) -> int:
+        """Number of stored states (emcee's ``sampler.iteration`` at thin_by = 1)."""
+        return self._iteration
+
+    def _stored(self, local: torch.Tensor, discard: int, thin: int, flat: bool) -> torch.Tensor:
+        """emcee's slicing of a stored quantity, gathered over the ranks: [n, W_total, ...] (flat: [n * W_total, ...])."""
+        if self._iteration == 0:
+            raise AttributeError("you must run the sampler with run_mcmc before accessing the results")
+        if discard < 0 or thin < 1:
+            raise ValueError("get_chain needs discard >= 0 and thin >= 1")
+        v = local[discard + thin - 1: self._iteration: thin]
+        if self.world > 1:  # walker-major for the row gather (one collective), then back to step-major
+            v = self._gather_rows(v.transpose(0, 1).contiguous()).transpose(0, 1)
+        v = v.contiguous()
+        return v.reshape((v.shape[0] * v.shape[1],) + tuple(v.shape[2:])) if flat else v
+
+    def get_chain(self, discard: int = 0, thin: int = 1, flat: bool = False) -> torch.Tensor:
+        """emcee's ``get_chain``: stored positions [discard + thin - 1 :: thin] as [n, W_total, ndim] (flat: [n * W_total,
+        ndim], step-major), on the ensemble's device, the same on every rank."""
+        return self._stored(self._chain, discard, thin, flat)
+
+    def get_log_prob(self, discard: int = 0, thin: int = 1, flat: bool = False) -> torch.Tensor:
+        """emcee's ``get_log_prob``: the stored log P, [n, W_total] (flat: [n * W_total])."""
+        return self._stored(self._chain_logp, discard, thin, flat)
+
+    def walker_acceptance_fraction(self) -> torch.Tensor:
+        """Per-walker accepted / steps made under run_mcmc, [W_total] float64 on the device: emcee's
+        ``sampler.acceptance_fraction`` at thin_by = 1 (``acceptance_fraction()`` is the ensemble-wide float)."""
+        if not isinstance(self.impl, NativeMoves):
+            raise NotImplementedError("per-walker accept counts come from the library's accept kernel; this moves_impl "
+                                      "reports none")
+        if self._mcmc_steps == 0:
+            raise AttributeError("you must run the sampler with run_mcmc before accessing the results")
+        counts = self._walker_acc if self.world == 1 else self._gather_rows(self._walker_acc)
+        return counts.to(torch.float64) / self._mcmc_steps
+
+    def get_autocorr_time(self, discard: int = 0, thin: int = 1, c: float = 5, tol: float = 50, quiet: bool = False):
+        """emcee's ``get_autocorr_time``: thin * integrated_time(get_chain(discard, thin)) (chain_stats.integrated_time)."""
+        from . import chain_stats
+
+        return thin * chain_stats.integrated_time(self.get_chain(discard=discard, thin=thin), c=c, tol=tol, quiet=quiet)
+
+    def gelman_rubin(self, discard: int = 0) -> torch.Tensor:
+        """What the reference's scripts print: ``gelman_rubin(sampler.get_chain(discard=discard, flat=False))``.  The scripts
+        pass the chain as emcee returns it, (steps, walkers, ndim), to a function whose comment says (nwalkers, nsamples,
+        ndim); the call is reproduced as they make it, so axis 0 (the steps) plays the "chains" and axis 1 (the walkers)
+        the "samples"."""
+        from . import chain_stats
+
+        return chain_stats.gelman_rubin(self.get_chain(discard=discard))
+
+    def percentile(self, q, discard: int = 0, thin: int = 1) -> torch.Tensor:
+        """``np.percentile(get_chain(discard, thin, flat=True), q, axis=0)`` computed on the device (same bits)."""
+        from . import chain_stats
+
+        return chain_stats.percentile(self.get_chain(discard=discard, thin=thin, flat=True), q)
 
     def full_state(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(positions [W_total, ndim], log-prob [W_total]) gathered on every rank (for tests / check-pointing)."""

@@ -462,6 +462,31 @@ int cf_ens_propose(int32_t kind, const double* d_all_pos, int64_t w_total, int32
 int cf_ens_accept(const int64_t* d_ids, const int64_t* d_local_idx, int64_t n_active, int32_t ndim, uint64_t key0,
                   const double* d_y, const double* d_lp_new, const double* d_log_factor, double* d_x_local,
                   double* d_logp_local, uint64_t* d_n_accepted, void* hip_stream);
+/* cf_ens_accept_record: cf_ens_accept (same d_x_local / d_logp_local / *d_n_accepted bits) that also records the step for
+ * a chain.  For every active walker it writes the walker's row after the accept to d_chain_slot [W_local * ndim] and its
+ * log P to d_logp_slot [W_local] at its local index, and adds its accept bit (0 / 1) to d_walker_accepted [W_local].
+ * Every walker is active in exactly one split of a step and no later split of the step moves it, so the accepts of one
+ * step's splits write every slot row once: the end-of-step state.  d_chain_slot and d_logp_slot are both null (count
+ * only) or both set; d_walker_accepted may be null (no per-walker counts). */
+int cf_ens_accept_record(const int64_t* d_ids, const int64_t* d_local_idx, int64_t n_active, int32_t ndim, uint64_t key0,
+                         const double* d_y, const double* d_lp_new, const double* d_log_factor, double* d_x_local,
+                         double* d_logp_local, uint64_t* d_n_accepted, double* d_chain_slot, double* d_logp_slot,
+                         int64_t* d_walker_accepted, void* hip_stream);
+
+/* ---- chain statistics (csrc/cosmofit_chain.hip): emcee's integrated autocorrelation time by direct lag sums ----------------
+ * A chain is [n_t, n_s] float64 in device memory, n_s = n_walkers * ndim series side by side (row t holds every series at
+ * step t: an emcee chain [n_t, n_w, ndim] as it lies in memory).  Every sum runs in a fixed order (no atomics), so the
+ * results are a deterministic function of the chain.
+ *   cf_chain_mean: d_mean [n_s] = per-series mean over t.
+ *   cf_chain_lagsum: d_out [nlag * n_s], row j = sum_{t < n_t - tau} (x_t - m)(x_{t + tau} - m) at tau = lag0 + j
+ *     (a lag >= n_t gives 0).
+ *   cf_chain_acf_mean: d_f [nlag * ndim], f[j][d] = (sum over w = 0 .. n_w - 1, ascending, of
+ *     d_lagsum[j][w ndim + d] / d_c0[w ndim + d]) / n_w, d_c0 = the lag-0 row. */
+int cf_chain_mean(const double* d_x, int64_t n_t, int64_t n_s, double* d_mean, void* hip_stream);
+int cf_chain_lagsum(const double* d_x, const double* d_mean, int64_t n_t, int64_t n_s, int64_t lag0, int32_t nlag,
+                    double* d_out, void* hip_stream);
+int cf_chain_acf_mean(const double* d_lagsum, const double* d_c0, int64_t n_w, int32_t ndim, int32_t nlag, double* d_f,
+                      void* hip_stream);
 
 #ifdef __cplusplus
 }
