@@ -15,8 +15,8 @@ from . import cmb_data, interpolator, laplace, likelihoods, scripts, solve_trian
 
 
 def __getattr__(name):
-    # `ensemble` and `chain_stats` need torch; import them lazily so that ctypes-only users do not pay for it
-    if name in ("ensemble", "chain_stats"):
+    # `ensemble`, `chain_stats` and `nested` need torch; import them lazily so that ctypes-only users do not pay for it
+    if name in ("ensemble", "chain_stats", "nested"):
         import importlib
         return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)

@@ -83,6 +83,15 @@ class cf_desc(C.Structure):
     ]
 
 
+CF_NS_MAX_NDIM = 16
+CF_NS_UNIFORM, CF_NS_NORMAL = 0, 1
+
+
+class cf_ns_prior(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("_pad", C.c_int32), ("kind", C.c_int32 * CF_NS_MAX_NDIM),
+                ("a", C.c_double * CF_NS_MAX_NDIM), ("b", C.c_double * CF_NS_MAX_NDIM)]
+
+
 class cf_info(C.Structure):
     _fields_ = [
         ("n_sn", C.c_int64), ("n_sn_pad", C.c_int64), ("packed_chol_bytes", C.c_int64),
@@ -136,6 +145,11 @@ EXPORTS = {
     "cf_chain_mean": (C.c_int, [_VP, _I64, _I64, _VP, _VP]),
     "cf_chain_lagsum": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _I32, _VP, _VP]),
     "cf_chain_acf_mean": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP]),
+    "cf_ns_prior_draw": (C.c_int, [_VP, _I64, C.c_uint64, _VP, _VP, _VP]),
+    "cf_ns_transform": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),
+    "cf_ns_walk_start": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _I64, C.c_uint64, _VP, _VP, _VP, _VP]),
+    "cf_ns_propose": (C.c_int, [_VP, _VP, _I64, _I64, C.c_uint64, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "cf_ns_accept": (C.c_int, [_I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cf_selftest_pack_host": (C.c_int, [_VP, _I64, _I64, _VP, C.POINTER(C.c_double), C.POINTER(_I64)]),
 }
 

@@ -488,6 +488,42 @@ int cf_chain_lagsum(const double* d_x, const double* d_mean, int64_t n_t, int64_
 int cf_chain_acf_mean(const double* d_lagsum, const double* d_c0, int64_t n_w, int32_t ndim, int32_t nlag, double* d_f,
                       void* hip_stream);
 
+/* ---- nested sampling (csrc/cosmofit_nested.hip; the driver is cosmology-model-fit_amd/nested.py) -------------------------
+ * Classic nested sampling with batch deletion on a device-resident live set: the per-step work of the constrained
+ * differential-evolution walk that replaces the dead points.  Points live in the unit cube; theta = T(u) is the prior
+ * transform of cf_ns_prior: lo + u (hi - lo) for CF_NS_UNIFORM (a = lo, b = hi), loc + scale * Phi^-1(u) for CF_NS_NORMAL
+ * (a = loc, b = scale).  Arrays are row-major [rows * ndim] float64 device pointers on the current device; every call is
+ * asynchronous on `hip_stream`.  Random numbers are the ensemble's counter-based generator: `key` is the 64-bit key of stream
+ * 0 for (seed, iteration, walk step) (nested.py: ns_key), stream s has key + s, the counter is the row index.
+ *   cf_ns_prior_draw: u[i][k] uniform in (0, 1) from stream k, theta = T(u), for i < n.
+ *   cf_ns_transform: theta = T(u) for n rows.
+ *   cf_ns_walk_start: walker i < m starts at survivor j = floor(U(stream 0, i) * n_surv): copies its u, theta, log L.
+ *   cf_ns_propose: partners a != b of the survivor set (streams 0 and 1), u' = u + gamma (u_a - u_b) + sigma N_k (normal k
+ *     from streams 2 + 2k, 3 + 2k); d_ok[i] = 1 and d_ptheta = T(u') if u' lies in the open cube, else d_ok[i] = 0 and
+ *     d_ptheta = the walker's current theta (the likelihood never sees a point outside the prior).
+ *   cf_ns_accept: walker i takes the proposal iff d_ok[i] and d_plogl[i] is finite and > *d_lstar; d_counts[0..2] +=
+ *     accepted, out-of-cube and non-finite proposals (integer atomics only). */
+#define CF_NS_MAX_NDIM 16
+enum { CF_NS_UNIFORM = 0, CF_NS_NORMAL = 1 };
+typedef struct cf_ns_prior {
+  int32_t ndim;                   /* 1 .. CF_NS_MAX_NDIM */
+  int32_t _pad;
+  int32_t kind[CF_NS_MAX_NDIM];   /* CF_NS_UNIFORM / CF_NS_NORMAL */
+  double a[CF_NS_MAX_NDIM];       /* lo / loc */
+  double b[CF_NS_MAX_NDIM];       /* hi / scale */
+} cf_ns_prior;
+
+int cf_ns_prior_draw(const cf_ns_prior* prior, int64_t n, uint64_t key, double* d_u, double* d_theta, void* hip_stream);
+int cf_ns_transform(const cf_ns_prior* prior, const double* d_u, int64_t n, double* d_theta, void* hip_stream);
+int cf_ns_walk_start(const double* d_su, const double* d_stheta, const double* d_slogl, int64_t n_surv, int32_t ndim, int64_t m,
+                     uint64_t key, double* d_wu, double* d_wtheta, double* d_wlogl, void* hip_stream);
+int cf_ns_propose(const cf_ns_prior* prior, const double* d_su, int64_t n_surv, int64_t m, uint64_t key, double gamma,
+                  double sigma, const double* d_wu, const double* d_wtheta, double* d_pu, double* d_ptheta, int32_t* d_ok,
+                  void* hip_stream);
+int cf_ns_accept(int64_t m, int32_t ndim, const double* d_lstar, const double* d_pu, const double* d_ptheta,
+                 const int32_t* d_ok, const double* d_plogl, double* d_wu, double* d_wtheta, double* d_wlogl,
+                 uint64_t* d_counts, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
