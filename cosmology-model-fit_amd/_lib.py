@@ -92,6 +92,21 @@ class cf_ns_prior(C.Structure):
                 ("a", C.c_double * CF_NS_MAX_NDIM), ("b", C.c_double * CF_NS_MAX_NDIM)]
 
 
+CF_QSR_BAO_NONE, CF_QSR_BAO_QUAD = 0, 1
+
+
+class cf_qsr_ext(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n_grid", C.c_int32), ("n_qsr", C.c_int64),
+        ("qsr_z", C.c_void_p), ("qsr_mu", C.c_void_p), ("qsr_sigma", C.c_void_p),
+        ("qsr_offset", cf_param), ("qsr_scatter", cf_param),
+        ("fde_n", C.c_double), ("fde_k", C.c_double), ("fde_p", C.c_double),
+        ("qsr_z_top", C.c_double), ("sn_z_top", C.c_double),
+        ("sn_zhel", C.c_int32), ("bao_mode", C.c_int32), ("n_bao", C.c_int32), ("_pad", C.c_int32),
+        ("bao_z", C.c_void_p), ("bao_val", C.c_void_p), ("bao_qty", C.c_void_p), ("bao_inv_cov", C.c_void_p),
+    ]
+
+
 class cf_info(C.Structure):
     _fields_ = [
         ("n_sn", C.c_int64), ("n_sn_pad", C.c_int64), ("packed_chol_bytes", C.c_int64),
@@ -151,6 +166,8 @@ EXPORTS = {
     "cf_ns_propose": (C.c_int, [_VP, _VP, _I64, _I64, C.c_uint64, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cf_ns_accept": (C.c_int, [_I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cf_selftest_pack_host": (C.c_int, [_VP, _I64, _I64, _VP, C.POINTER(C.c_double), C.POINTER(_I64)]),
+    "cf_create_quasar": (C.c_int, [C.POINTER(cf_desc), C.POINTER(cf_qsr_ext), C.POINTER(_VP)]),
+    "cf_qsr_eval_parts": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP]),
 }
 
 

@@ -312,6 +312,16 @@ struct PinnedBuf {
 #define CF_NP2_FROM 512  // walkers: 32-walker panels in the throughput solve kernel beyond this batch size, 16-walker panels up to it
 #endif
 
+// The quasar Hubble-diagram likelihoods (cosmofit_quasar.hip): create-time tables and the per-walker kernel's launch.
+struct cf_qsr_state;
+int cf_qsr_prepare(const cf_desc* c, const cf_qsr_ext* e, int64_t n_ld, cf_qsr_state** out);
+void cf_qsr_free(cf_qsr_state* q);
+int64_t cf_qsr_n_qsr(const cf_qsr_state* q);
+int32_t cf_qsr_n_bao(const cf_qsr_state* q);
+void cf_qsr_set_outputs(cf_qsr_state* q, double* parts, double* mu_sn, double* mu_q, double* bao);
+int cf_qsr_launch(const cf_qsr_state* q, const double* theta, int64_t W, double* delta, double* extra, int out_kind, double* th_copy,
+                  hipStream_t st);
+
 // A host thread that evaluates one replica's slice of a multi-device cf_eval (one per replica beyond the first).
 struct cf_worker {
   std::thread th;
@@ -356,6 +366,7 @@ struct cf_handle {
   bool theta_on_host = false;     // set around a zero-copy evaluation: theta is the pinned staging block (reads cross the host link)
   bool has_small_blocks = false;  // BAO and / or CMB block present
   bool has_growth = false;        // growth-rate block present
+  cf_qsr_state* qsr = nullptr;    // a quasar likelihood (cf_create_quasar): its per-walker kernel replaces walker_kernel
   int64_t max_walkers = 0;
   double pack_probe_rel = 0.0;
   int cu_count = 0;
@@ -1066,6 +1077,7 @@ extern "C" void cf_destroy(cf_handle* h) {
   for (auto& e : h->ev)
     if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
+  cf_qsr_free(h->qsr);
   delete h;
 }
 
@@ -1305,15 +1317,21 @@ static int launch_eval(cf_handle* h, const double* th, int64_t Wc, double* out, 
   double* delta = h->delta.as<double>();
   d2* bao_nodes = h->bao_nodes.as<d2>();
   if (ev) HIP_TRY(hipEventRecord(ev[0], st));
-  if (ev && !(h->d.n_sn > 0 || h->has_small_blocks || h->has_growth)) HIP_TRY(hipEventRecord(ev[1], st));
+  if (ev && !(h->d.n_sn > 0 || h->has_small_blocks || h->has_growth || h->qsr)) HIP_TRY(hipEventRecord(ev[1], st));
   const bool walker_work = d.n_sn > 0 || h->has_small_blocks || h->has_growth;
-  double* extra = (h->has_small_blocks || h->has_growth) ? h->chi2_extra.as<double>() : nullptr;
+  double* extra = (h->has_small_blocks || h->has_growth || h->qsr) ? h->chi2_extra.as<double>() : nullptr;
   // a small batch of the production path: walker_fast_kernel writes the residuals in the fragment order the small-batch solve
   // kernel loads them in (one contiguous 1 KiB load per K-step pair instead of a 16-row gather: sn_fast_loop, FRAG)
   static const bool frag_env = cf_tune("small_frag", 1) != 0;
   const bool small_solve = d.n_sn > 0 && h->solve_mode == CF_SOLVE_INVERSE_GEMM && h->partial4.p && Wc <= small_batch_max();
-  const bool frag_b = frag_env && small_solve && !dm_out && !mucorr_out && walker_fast_ok(d);
-  if (walker_work) {
+  const bool frag_b = frag_env && small_solve && !dm_out && !mucorr_out && walker_fast_ok(d) && !h->qsr;
+  if (h->qsr) {  // quasar likelihood: its own per-walker kernel writes the SN residuals (row layout) and the quasar / BAO chi^2
+    double* th_copy = h->theta_on_host ? h->theta.as<double>() : nullptr;
+    int rc = cf_qsr_launch(h->qsr, th, Wc, delta, extra, out_kind, th_copy, st);
+    if (rc) return rc;
+    if (th_copy) th = th_copy;
+    if (ev) HIP_TRY(hipEventRecord(ev[1], st));
+  } else if (walker_work) {
     // skewed {cum, dh} table: one spare 16-byte slot per 2^chunk_shift nodes
     const size_t lds = ((size_t)d.n_grid + (d.n_grid >> d.chunk_shift) + 2) * 16;
     if (!dm_out && !mucorr_out && walker_fast_ok(d)) {  // the production form: lean kernel arguments, theta row across the lanes
@@ -1588,6 +1606,7 @@ extern "C" int cf_eval(cf_handle* h, const double* theta, int64_t W, double* out
 extern "C" int cf_eval_parts(cf_handle* h, const double* theta, int64_t W, double* dm_obs, double* mu_corr,
                              double* delta, double* chi2_blocks, double* bao_theory, double* fs8_theory) {
   if (!h || !theta) return fail(CF_ERR_INVALID, "cf_eval_parts: null argument");
+  if (h->qsr) return fail(CF_ERR_UNSUPPORTED, "cf_eval_parts: a quasar handle; use cf_qsr_eval_parts");
   if (W <= 0 || W > (1 << 20)) return fail(CF_ERR_INVALID, "cf_eval_parts: W out of range");
   if (bao_theory && h->d.n_bao == 0) return fail(CF_ERR_INVALID, "cf_eval_parts: this likelihood has no BAO block");
   if (fs8_theory && h->d.n_fs8 == 0) return fail(CF_ERR_INVALID, "cf_eval_parts: this likelihood has no growth-rate block");
@@ -1645,6 +1664,7 @@ extern "C" int cf_eval_parts(cf_handle* h, const double* theta, int64_t W, doubl
 // DM_z(params, z) of the scripts interpolates (sn/pantheon.py:34-40).  Only the table build of walker_kernel runs.
 extern "C" int cf_eval_table(cf_handle* h, const double* theta, int64_t W, double* cum_dm, double* dh) {
   if (!h || !theta || !cum_dm || !dh) return fail(CF_ERR_INVALID, "cf_eval_table: null argument");
+  if (h->qsr) return fail(CF_ERR_UNSUPPORTED, "cf_eval_table: a quasar handle; use cf_qsr_eval_parts");
   if (W <= 0 || W > 4096) return fail(CF_ERR_INVALID, "cf_eval_table: W must be in 1..4096");
   std::lock_guard<std::mutex> lk(h->mu);
   DeviceScope on_device(h->device);
@@ -1735,6 +1755,7 @@ extern "C" int cf_eval_fs8_at(cf_handle* h, const double* theta, const double* z
 
 extern "C" int cf_eval_hz(cf_handle* h, const double* theta, const double* z, int64_t n, double* out) {
   if (!h || !theta || (n > 0 && (!z || !out))) return fail(CF_ERR_INVALID, "cf_eval_hz: null argument");
+  if (h->qsr) return fail(CF_ERR_UNSUPPORTED, "cf_eval_hz: a quasar handle; use cf_qsr_eval_parts");
   if (n < 0) return fail(CF_ERR_INVALID, "cf_eval_hz: n must be >= 0");
   if (n == 0) return CF_OK;
   std::lock_guard<std::mutex> lk(h->mu);
@@ -1757,6 +1778,7 @@ extern "C" int cf_eval_hz(cf_handle* h, const double* theta, const double* z, in
 
 extern "C" int cf_eval_bao_at(cf_handle* h, const double* theta, const double* z, const int32_t* qty, int64_t n, double* out) {
   if (!h || !theta || (n > 0 && (!z || !qty || !out))) return fail(CF_ERR_INVALID, "cf_eval_bao_at: null argument");
+  if (h->qsr) return fail(CF_ERR_UNSUPPORTED, "cf_eval_bao_at: a quasar handle; use cf_qsr_eval_parts");
   if (n < 0) return fail(CF_ERR_INVALID, "cf_eval_bao_at: n must be >= 0");
   for (int64_t k = 0; k < n; ++k) {
     if (!std::isfinite(z[k])) return fail(CF_ERR_INVALID, "cf_eval_bao_at: z must be finite");
@@ -1939,5 +1961,75 @@ extern "C" int cf_selftest_pack_host(const double* L, int64_t n, int64_t ld, con
   if (pack_default(L, n, ld, hp) != 0) return fail(CF_ERR_NOT_POSDEF, "cf_selftest_pack_host: bad pivot");
   *chi2_out = cf_pack_replay_host(hp, b);
   if (packed_bytes) *packed_bytes = (int64_t)(hp.frags.size() * sizeof(cf_d2));
+  return CF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Quasar Hubble-diagram likelihoods (include/cosmofit.h: cf_create_quasar): an ordinary handle whose per-walker kernel is
+// cosmofit_quasar.hip's; the SN solve, the epilogue, the workspace, timing and the completion words are the handle's own.
+// ------------------------------------------------------------------------------------------------
+extern "C" int cf_create_quasar(const cf_desc* c, const cf_qsr_ext* e, cf_handle** out) {
+  if (!c || !e || !out) return fail(CF_ERR_INVALID, "cf_create_quasar: null argument");
+  *out = nullptr;
+  if (c->n_devices != 0) return fail(CF_ERR_UNSUPPORTED, "cf_create_quasar: a quasar handle lives on one device (n_devices must be 0)");
+  int rc = validate_desc(c);
+  if (rc) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(CF_ERR_NO_DEVICE, "cf_create_quasar: no HIP device visible (this library has no CPU path)");
+  if (c->device < 0 || c->device >= ndev) return fail(CF_ERR_INVALID, "cf_create_quasar: device ordinal out of range");
+  HostPrep prep;
+  cf_handle* h = nullptr;
+  if ((rc = create_one(c, c->device, prep, &h))) return rc;
+  {
+    DeviceScope on_device(h->device);
+    if (on_device.err != hipSuccess) rc = fail(CF_ERR_HIP, "hipSetDevice failed");
+    else rc = cf_qsr_prepare(c, e, h->d.n_ld, &h->qsr);
+  }
+  if (rc) {
+    const std::string keep = g_err;
+    cf_destroy(h);
+    return fail(rc, keep);
+  }
+  *out = h;
+  return CF_OK;
+}
+
+extern "C" int cf_qsr_eval_parts(cf_handle* h, const double* theta, int64_t W, double* chi2_blocks, double* mu_sn, double* mu_qsr,
+                                 double* bao_theory) {
+  if (!h || !theta) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: null argument");
+  if (!h->qsr) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: not a quasar handle (cf_create_quasar)");
+  if (W <= 0 || W > (1 << 20)) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: W out of range");
+  if (mu_sn && h->d.n_sn == 0) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: this likelihood has no SN block");
+  const int64_t nq = cf_qsr_n_qsr(h->qsr), nb = cf_qsr_n_bao(h->qsr), n = h->d.n_sn;
+  if (bao_theory && nb == 0) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: this likelihood has no BAO block");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceScope on_device(h->device);
+  HIP_TRY(on_device.err);
+  int rc;
+  if ((rc = ensure_workspace(h, W))) return rc;
+  DevBuf parts, snb, ms, mq, bt;
+  if (parts.ensure((size_t)W * 3 * 8) || snb.ensure((size_t)W * 8)) return CF_ERR_HIP;
+  HIP_TRY(hipMemsetAsync(parts.p, 0, (size_t)W * 3 * 8, h->stream));
+  HIP_TRY(hipMemsetAsync(snb.p, 0, (size_t)W * 8, h->stream));
+  if (mu_sn && ms.ensure((size_t)W * n * 8)) return CF_ERR_HIP;
+  if (mu_qsr && mq.ensure((size_t)W * nq * 8)) return CF_ERR_HIP;
+  if (bao_theory && bt.ensure((size_t)W * nb * 8)) return CF_ERR_HIP;
+  HIP_TRY(hipMemcpyAsync(h->theta.p, theta, (size_t)W * h->d.ndim * 8, hipMemcpyHostToDevice, h->stream));
+  cf_qsr_set_outputs(h->qsr, parts.as<double>(), ms.as<double>(), mq.as<double>(), bt.as<double>());
+  rc = launch_path(h, h->theta.as<const double>(), W, h->out.as<double>(), CF_OUT_CHI2, h->stream, nullptr, nullptr, nullptr, nullptr,
+                   n > 0 ? snb.as<double>() : nullptr);
+  cf_qsr_set_outputs(h->qsr, nullptr, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (mu_sn) HIP_TRY(hipMemcpy(mu_sn, ms.p, (size_t)W * n * 8, hipMemcpyDeviceToHost));
+  if (mu_qsr) HIP_TRY(hipMemcpy(mu_qsr, mq.p, (size_t)W * nq * 8, hipMemcpyDeviceToHost));
+  if (bao_theory) HIP_TRY(hipMemcpy(bao_theory, bt.p, (size_t)W * nb * 8, hipMemcpyDeviceToHost));
+  if (chi2_blocks) {
+    std::vector<double> sn((size_t)W);
+    HIP_TRY(hipMemcpy(chi2_blocks, parts.p, (size_t)W * 3 * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sn.data(), snb.p, (size_t)W * 8, hipMemcpyDeviceToHost));
+    for (int64_t w = 0; w < W; ++w) chi2_blocks[3 * w] = sn[(size_t)w];
+  }
   return CF_OK;
 }

@@ -173,6 +173,39 @@ struct cf_epilogue {
 };
 #define CF_EPI_WORDS ((int)((sizeof(cf_epilogue) + 7) / 8))
 
+// Quasar Hubble-diagram likelihoods (cosmofit_quasar.hip): the per-walker kernel's arguments.  Every table is theta-independent
+// and built at cf_create_quasar: per grid node the trapezoid width, (1 + z)^3 and ln(n X / (1 + (n - 1) X)), X = (1 + z)^k.
+// Table 0 is the quasar grid, table 1 the SN grid when the SN block has one of its own (two_grids), then one table per distinct
+// BAO redshift whose width entry is the node's trapezoid WEIGHT instead (only the last value of those integrals is used).
+struct cf_qsr_args {
+  int32_t ndim, n_grid;
+  int32_t n_sn, n_ld;
+  int32_t n_qsr, two_grids;
+  int32_t n_bao, n_bz;  // BAO data, distinct BAO redshifts
+  double c, fde_a;      // c in km/s; f_DE exponent per unit (1 + w0): p
+  cf_dev_slot om, w0, h0, off_sn, off_q, scat, rd;
+  const double* node_w;    // [tables][n_grid] trapezoid widths z_j - z_{j-1} (0 at j = 0) / BAO weights
+  const double* node_zp3;  // [tables][n_grid]
+  const double* node_lnf;  // [tables][n_grid]
+  // interpolation records: grid node j, z - z_j (0 = exactly node j, also at / above the top: np.interp), z_{j+1} - z_j
+  const int32_t* sn_j;
+  const double* sn_t;
+  const double* sn_h;
+  const double* sn_zp1;  // 1 + z (or 1 + z_hel) of the luminosity distance
+  const double* sn_obs;
+  const int32_t* q_j;
+  const double* q_t;
+  const double* q_h;
+  const double* q_zp1;
+  const double* q_mu;
+  const double* q_var;   // sigma^2
+  const double* bao_z;
+  const double* bao_val;
+  const double* bao_inv;
+  const int32_t* bao_qty;
+  const int32_t* bao_zi;  // [n_bao] distinct-redshift table of datum k
+};
+
 #ifdef __HIPCC__
 typedef double cf_d2 __attribute__((ext_vector_type(2)));
 #else

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "cosmofit_device.h"
+#include "cf_wave_scan.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -433,25 +434,7 @@ __device__ __forceinline__ double log10_tab(double x, const d2* __restrict__ tab
   return fma_vsv(ek, log10_2hi, t.y) + fma(r, p, ek * log10_2lo);
 }
 
-// Inclusive scan across the 64 lanes of a wave on DPP row operations (no LDS round trips, unlike
-// ds_bpermute-based shuffles): Hillis-Steele inside each row of 16 lanes (row_shr 1, 2, 4, 8), then
-// lane 15 of rows 0 / 2 into rows 1 / 3 (row_bcast:15) and lane 31 into rows 2-3 (row_bcast:31).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_move(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xF, false);
-  return __hiloint2double(hi, lo);  // lanes without a source (or outside ROW_MASK) get 0
-}
-
-__device__ __forceinline__ double wave_inclusive_scan(double v) {
-  v += dpp_move<0x111, 0xF>(v);  // row_shr:1
-  v += dpp_move<0x112, 0xF>(v);  // row_shr:2
-  v += dpp_move<0x114, 0xF>(v);  // row_shr:4
-  v += dpp_move<0x118, 0xF>(v);  // row_shr:8
-  v += dpp_move<0x142, 0xA>(v);  // row_bcast:15 -> rows 1 and 3
-  v += dpp_move<0x143, 0xC>(v);  // row_bcast:31 -> rows 2 and 3
-  return v;
-}
+// dpp_move / wave_inclusive_scan: cf_wave_scan.h
 
 // Build the table.  All CF_TPB_A threads call it.
 //   dh[g]  = c/H(z_g)

@@ -52,7 +52,8 @@ class LikelihoodEngine:
                  bao: Optional[dict] = None, cmb: Optional[dict] = None, physical: Optional[dict] = None,
                  cc: Optional[dict] = None, fs8: Optional[dict] = None, solve_mode: int = L.CF_SOLVE_AUTO,
                  bounds=None, gauss: Sequence = (), chi2_gauss: Sequence = (), cpl_wall: bool = False,
-                 device: int = 0, devices=None, probe_limit: float = 0.0, om_mode: int = 0, logl_const: float = 0.0, prior_normalised: bool = True, c_km_s: float = C_KM_S):
+                 device: int = 0, devices=None, probe_limit: float = 0.0, om_mode: int = 0, logl_const: float = 0.0, prior_normalised: bool = True, c_km_s: float = C_KM_S,
+                 quasar: Optional[dict] = None):
         """
         params: {"H0": Param(1), "Om": Param(2), ...} for the slots of include/cosmofit.h (cf_param_slot).
         sn: dict(z_cmb, z_hel, obs, chol[, step | z_turn, fixed_mu, lin_coef, dirs]) — chol is
@@ -78,6 +79,9 @@ class LikelihoodEngine:
             the packed factor are replicated on each, and the host-buffer calls (chi_squared / log_likelihood /
             log_probability) split their rows over them -- one host process, as emcee / nautilus run, on every GPU.
         probe_limit: acceptance limit of the create-time accuracy probe of the explicit inverse (0 = default 1e-11).
+        quasar: dict(z, mu, sigma, offset: Param, scatter: Param, nkp (n, k, p), z_top[, sn_z_top=0, sn_zhel=False,
+            bao=dict(z, val, qty, inv_cov)]) -- a quasar Hubble-diagram likelihood (include/cosmofit.h: cf_create_quasar,
+            quasars.py builds it from a recipe); `bao` then goes here, not in the descriptor.
         solve_mode: CF_SOLVE_AUTO (default: the inverse-GEMM solve when its create-time probe passes, otherwise the
             blocked forward substitution), CF_SOLVE_INVERSE_GEMM or CF_SOLVE_BLOCKED_TRSM; info()["solve_mode"]
             tells which one runs.  See solve_mode_of() for the keyword form the mirrors take.
@@ -202,7 +206,33 @@ class LikelihoodEngine:
         self.n_sn = int(d.n_sn)
         self._h = C.c_void_p()
         self._cf_eval = lib.cf_eval
-        L.check(lib.cf_create(C.byref(d), C.byref(self._h)))
+        self.n_qsr = 0
+        if quasar is None:
+            L.check(lib.cf_create(C.byref(d), C.byref(self._h)))
+        else:
+            e = L.cf_qsr_ext()
+            e.struct_size, e.n_grid = C.sizeof(L.cf_qsr_ext), int(n_grid)
+            qz, qmu, qsig = _f64(quasar["z"]), _f64(quasar["mu"]), _f64(quasar["sigma"])
+            if not (qz.size == qmu.size == qsig.size):
+                raise ValueError("quasar: z, mu, sigma must have the same length")
+            keep += [qz, qmu, qsig]
+            e.n_qsr, e.qsr_z, e.qsr_mu, e.qsr_sigma = qz.size, _ptr(qz), _ptr(qmu), _ptr(qsig)
+            for name in ("offset", "scatter"):
+                p, slot = quasar[name], getattr(e, "qsr_" + name)
+                slot.idx, slot.scale, slot.fixed = p.idx, p.scale, p.fixed
+            e.fde_n, e.fde_k, e.fde_p = (float(x) for x in quasar["nkp"])
+            e.qsr_z_top, e.sn_z_top = float(quasar["z_top"]), float(quasar.get("sn_z_top", 0.0))
+            e.sn_zhel = 1 if quasar.get("sn_zhel", False) else 0
+            qb = quasar.get("bao")
+            if qb is not None:
+                bz, bv, binv = _f64(qb["z"]), _f64(qb["val"]), _f64(qb["inv_cov"])
+                bq = np.ascontiguousarray(qb["qty"], dtype=np.int32)
+                keep += [bz, bv, binv, bq]
+                e.bao_mode, e.n_bao = L.CF_QSR_BAO_QUAD, bz.size
+                e.bao_z, e.bao_val, e.bao_qty, e.bao_inv_cov = _ptr(bz), _ptr(bv), _ptr(bq), _ptr(binv)
+                self.n_bao = int(bz.size)
+            self.n_qsr = int(qz.size)
+            L.check(lib.cf_create_quasar(C.byref(d), C.byref(e), C.byref(self._h)))
         del keep  # cf_create copied everything
 
     # ---- lifetime ---------------------------------------------------------------------------
@@ -287,6 +317,18 @@ class LikelihoodEngine:
         L.check(L.lib().cf_eval_parts(self._h, _ptr(th), W, _ptr(dm), _ptr(mc), _ptr(dl), _ptr(blocks), _ptr(bt), _ptr(ft)))
         return dict(dm=dm, mu_corr=mc, delta=dl, chi2_blocks=blocks[:, :3], cmb_vector=blocks[:, 3:6], chi2_cc=blocks[:, 6],
                     chi2_fs8=blocks[:, 7], z_star=blocks[:, 8], r_drag=blocks[:, 9], bao_theory=bt, fs8_theory=ft)
+
+    def quasar_parts(self, theta):
+        """Per-block results of a quasar likelihood (cf_qsr_eval_parts) for a batch: chi2_blocks [W, 3] = (sn, quasar, BAO),
+        mu_sn [W, n_sn], mu_qsr [W, n_qsr], bao_theory [W, n_bao] (None for an absent block)."""
+        th = np.atleast_2d(_f64(theta))
+        W = th.shape[0]
+        blocks = np.empty((W, 3))
+        ms = np.empty((W, self.n_sn)) if self.n_sn else None
+        mq = np.empty((W, self.n_qsr))
+        bt = np.empty((W, self.n_bao)) if self.n_bao else None
+        L.check(L.lib().cf_qsr_eval_parts(self._h, _ptr(th), W, _ptr(blocks), _ptr(ms), _ptr(mq), _ptr(bt)))
+        return dict(chi2_blocks=blocks, mu_sn=ms, mu_qsr=mq, bao_theory=bt)
 
     def distance_table(self, theta):
         """(z_grid [G], cum_dm [W, G], dh_grid [W, G]) of one theta or a small batch: the grid of the scripts

@@ -189,7 +189,10 @@ class Joint(_Base):
 
 
 def build(script: str, **data) -> Joint:
-    """``build("bao/desi_des5y_cc.py", sn=..., bao=..., cc=...)``."""
+    """``build("bao/desi_des5y_cc.py", sn=..., bao=..., cc=...)``; names under quasars/ go to ``quasars.build``."""
+    if script.startswith("quasars/"):
+        from . import quasars
+        return quasars.build(script, **data)
     if script not in RECIPES:
         raise KeyError(f"no recipe for {script!r}; known: {sorted(RECIPES)}")
     return Joint(RECIPES[script], **data)

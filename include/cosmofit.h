@@ -524,6 +524,55 @@ int cf_ns_accept(int64_t m, int32_t ndim, const double* d_lstar, const double* d
                  const int32_t* d_ok, const double* d_plogl, double* d_wu, double* d_wtheta, double* d_wlogl,
                  uint64_t* d_counts, void* hip_stream);
 
+/* ---- quasar Hubble-diagram likelihoods (csrc/cosmofit_quasar.hip; the recipes are cosmology-model-fit_amd/quasars.py) ----
+ * The quasars/qsr_*.py scripts: Risaliti-Lusso quasars as standard candles with a free intrinsic scatter, alone or joint
+ * with SNe and BAO, on an older distance algorithm than the other scripts:
+ *   E^2 = Om (1+z)^3 + (1 - Om) f_DE,  f_DE = (n X / (1 + (n - 1) X))^(p (1 + w0)),  X = (1+z)^k;
+ *   I(z) = np.interp(z, grid, cumulative_trapezoid(1 / E, grid, initial=0)), grid = linspace(0, top, n_grid);
+ *   mu(z) = 25 + 5 log10((1 + z') (c / H0) I(z)),  z' = z, or z_hel for the SN block when sn_zhel = 1;
+ *   chi2_q = sum delta^2 / (sigma^2 + s^2),  delta = mu_obs - dM_qsr - mu(z),  log L -= 0.5 sum ln(sigma^2 + s^2);
+ *   the SN block is the descriptor's: residual obs - offset - mu(z_cmb), chi2 through its Cholesky factor;
+ *   BAO (bao_mode = CF_QSR_BAO_QUAD): D_M(z_i) = c / H0 x the trapezoid of 1 / E on linspace(0, z_i, n_grid) of its own,
+ *   D_H = c / H(z_i), D_V = (z D_H D_M^2)^(1/3), all over r_d (slot CF_P_RD); chi2_bao = Delta^T inv_cov Delta.
+ * cf_create_quasar takes an ordinary cf_desc for what the scripts share with the rest (ndim, device, c_km_s, slots CF_P_OM,
+ * CF_P_W0, CF_P_H0, CF_P_OFFSET (SN offset), CF_P_RD, the SN block, bounds, solve_mode; ez_model CF_EZ_LATE_FLAT, fde, n_grid
+ * and z_max are not used by the quasar path, n_bao / cmb / cc / fs8 must be absent) plus this extension.  The result is an
+ * ordinary handle: cf_eval, cf_eval_device, timing and cf_destroy work on it; cf_eval_parts, cf_eval_table, cf_eval_bao_at,
+ * cf_eval_hz and cf_eval_fs8_at refuse it (CF_ERR_UNSUPPORTED), cf_qsr_eval_parts is its accessor.
+ *   CF_OUT_CHI2 = chi2_sn + chi2_q + chi2_bao ("chi squared total" of the scripts), CF_OUT_LOGL = the script's log_likelihood,
+ *   CF_OUT_LOGP = its log_posterior (strict box, 0 inside: prior_norm_mode = 1).
+ * One device only: a descriptor with n_devices != 0 is refused with CF_ERR_UNSUPPORTED. */
+enum cf_qsr_bao_mode { CF_QSR_BAO_NONE = 0, CF_QSR_BAO_QUAD = 1 };
+#define CF_QSR_MAX_QSR 65536
+typedef struct cf_qsr_ext {
+  int32_t struct_size;      /* sizeof(cf_qsr_ext) as seen by the caller */
+  int32_t n_grid;           /* nodes of every linspace grid (3000 in the scripts), 16 .. 8192 */
+  int64_t n_qsr;            /* 1 .. CF_QSR_MAX_QSR */
+  const double* qsr_z;      /* [n_qsr] */
+  const double* qsr_mu;     /* [n_qsr] observed distance moduli */
+  const double* qsr_sigma;  /* [n_qsr] */
+  cf_param qsr_offset;      /* dM_qsr */
+  cf_param qsr_scatter;     /* s */
+  double fde_n, fde_k, fde_p;  /* (n, k, p) of f_DE */
+  double qsr_z_top;         /* top of the quasar grid (max z_qsr in every script) */
+  double sn_z_top;          /* top of a separate SN grid (max z_sn), or 0: the SN block reads the quasar grid */
+  int32_t sn_zhel;          /* 1: the SN luminosity distance takes (1 + z_hel) */
+  int32_t bao_mode;         /* cf_qsr_bao_mode */
+  int32_t n_bao;            /* 0 .. 64 */
+  int32_t _pad;
+  const double* bao_z;      /* [n_bao] */
+  const double* bao_val;    /* [n_bao] */
+  const int32_t* bao_qty;   /* [n_bao] CF_BAO_DV / CF_BAO_DM / CF_BAO_DH */
+  const double* bao_inv_cov;/* [n_bao * n_bao] row-major inverse covariance */
+} cf_qsr_ext;
+
+int cf_create_quasar(const cf_desc* desc, const cf_qsr_ext* ext, cf_handle** out);
+/* Per-block results of a quasar handle for W host rows, computed by the same kernels as cf_eval.  Any output may be NULL.
+ *   chi2_blocks [W * 3]  (chi2_sn, chi2_q, chi2_bao), 0 for an absent block
+ *   mu_sn [W * n_sn], mu_qsr [W * n_qsr]  mu at the SN and quasar redshifts;  bao_theory [W * n_bao]  the BAO predictions */
+int cf_qsr_eval_parts(cf_handle* h, const double* theta, int64_t W, double* chi2_blocks, double* mu_sn, double* mu_qsr,
+                      double* bao_theory);
+
 #ifdef __cplusplus
 }
 #endif
