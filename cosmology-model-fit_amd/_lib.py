@@ -94,6 +94,22 @@ class cf_ns_prior(C.Structure):
 
 CF_QSR_BAO_NONE, CF_QSR_BAO_QUAD = 0, 1
 
+CF_OPT_MAX_NDIM, CF_OPT_MAX_TRIALS = 16, 8
+CF_OPT_RUNNING, CF_OPT_CONVERGED, CF_OPT_NOISE_FLOOR, CF_OPT_ITER_CAP, CF_OPT_NONFINITE_START, CF_OPT_NONFINITE_STENCIL = range(6)
+CF_OPT_NEED_RESET, CF_OPT_HAS_PAIR, CF_OPT_FRESH, CF_OPT_HAS_STEP = 1, 2, 4, 8
+
+
+class cf_opt_params(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("n_free", C.c_int32), ("free_idx", C.c_int32 * CF_OPT_MAX_NDIM),
+                ("lo", C.c_double * CF_OPT_MAX_NDIM), ("width", C.c_double * CF_OPT_MAX_NDIM), ("h", C.c_double),
+                ("delta", C.c_double), ("c1", C.c_double), ("gtol", C.c_double), ("gtol_rel", C.c_double),
+                ("n_trials", C.c_int32), ("max_iter", C.c_int32)]
+
+
+class cf_opt_state(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("u", "f", "g", "g_prev", "s", "hinv", "d", "gnorm", "form", "status", "n_iter",
+                                                "flags")]
+
 
 class cf_qsr_ext(C.Structure):
     _fields_ = [
@@ -168,6 +184,11 @@ EXPORTS = {
     "cf_selftest_pack_host": (C.c_int, [_VP, _I64, _I64, _VP, C.POINTER(C.c_double), C.POINTER(_I64)]),
     "cf_create_quasar": (C.c_int, [C.POINTER(cf_desc), C.POINTER(cf_qsr_ext), C.POINTER(_VP)]),
     "cf_qsr_eval_parts": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "cf_opt_starts": (C.c_int, [C.POINTER(cf_opt_params), _I64, _VP, C.c_uint64, _I32, _VP, _VP, _VP]),
+    "cf_opt_stencil": (C.c_int, [C.POINTER(cf_opt_params), C.POINTER(cf_opt_state), _VP, _I64, _VP, _VP]),
+    "cf_opt_direction": (C.c_int, [C.POINTER(cf_opt_params), C.POINTER(cf_opt_state), _VP, _I64, _VP, _VP, _VP]),
+    "cf_opt_accept": (C.c_int, [C.POINTER(cf_opt_params), C.POINTER(cf_opt_state), _VP, _I64, _VP, _VP]),
+    "cf_opt_compact": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP]),
 }
 
 

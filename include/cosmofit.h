@@ -573,6 +573,81 @@ int cf_create_quasar(const cf_desc* desc, const cf_qsr_ext* ext, cf_handle** out
 int cf_qsr_eval_parts(cf_handle* h, const double* theta, int64_t W, double* chi2_blocks, double* mu_sn, double* mu_qsr,
                       double* bao_theory);
 
+/* ---- batched box-constrained maximization (csrc/cosmofit_opt.hip; the driver is cosmology-model-fit_amd/optimize.py) -----
+ * B independent problems maximise one objective f(theta) inside a box.  A problem lives in box-scaled coordinates
+ * u = (theta - lo) / width, u in [delta, 1 - delta]; theta = lo + u width is every row the objective sees.  The n_free
+ * coordinates free_idx move (common to all problems); the others keep each problem's start value.  Per iteration:
+ *   cf_opt_stencil: for every active problem a (problem d_active[a]) the 2 n_free rows d_rows [(a 2 n_free + 2 j + side) * ndim]:
+ *     free slot j perturbed by u +- h (central form 0), u + h, u + 2h (forward form +1, within 2h of the lower face) or
+ *     u - h, u - 2h (backward form -1, within 2h of the upper face); writes the forms.
+ *   cf_opt_direction: 16 lanes per problem from the stencil values d_fs: the gradient g (free slots), the projected gradient
+ *     (a slot at a face with g pointing out of the box is held at 0), its max norm; status CF_OPT_NONFINITE_STENCIL if a
+ *     stencil value is not finite, CF_OPT_CONVERGED if the norm <= gtol + gtol_rel |f|; else the BFGS update of H^-1 on -f
+ *     (y = g_prev - g zeroed on the held slots; skipped when s.y <= 0 or (s.y)^2 <= 1e-20 |s|^2 |y|^2), d = H^-1 pg
+ *     (held slots 0), a reset to sigma I when flagged or when pg.d <= 0 (sigma: the largest move 0.1, or min(0.1, 4 max|s|)
+ *     once a step was taken; after a failed search at most 4^-K max|d| of the failed direction), and the K trial rows
+ *     d_trials [(a K + k) * ndim] = P(u + 4^-k d) (P clamps to [delta, 1 - delta]; a finished problem gets K copies of u).
+ *   cf_opt_accept: one thread per problem from the trial values d_ft: the first k with f_k >= f + c1 g.(u_k - u), else the
+ *     best finite f_k; a trial counts only if f_k > f + 4 eps |f|; else a reset next iteration (CF_OPT_NOISE_FLOOR if H^-1
+ *     was fresh from a reset after a failed search); n_iter += 1, CF_OPT_ITER_CAP at max_iter.
+ *   cf_opt_compact: one workgroup: the still-running problems of d_active in order into d_next, their number into *d_count.
+ * cf_opt_starts: u for n rows: a free coordinate uniform in [delta, 1 - delta] from stream c (the coordinate) at counter b
+ *   (the row) of the ensemble's counter-based generator under `key` (optimize.py: opt_key) when `random`, else
+ *   clamp((x0 - lo) / width); a fixed coordinate always from d_x0 [n * ndim]; d_theta = lo + u width.
+ * Per-problem state (cf_opt_state): row-major float64 device arrays, problem b at b * ndim (u), b * 16 (g, g_prev, s, d,
+ * form), b * 256 (hinv, row i of H^-1 at 16 i) and b (f, gnorm, status, n_iter, flags).  Every call is asynchronous on
+ * `hip_stream`; sums run in index order and there are no float atomics, so a problem's bits do not depend on the batch. */
+#define CF_OPT_MAX_NDIM 16
+#define CF_OPT_MAX_TRIALS 8
+enum cf_opt_status {
+  CF_OPT_RUNNING = 0,
+  CF_OPT_CONVERGED = 1,         /* projected, box-scaled gradient <= gtol + gtol_rel |f| */
+  CF_OPT_NOISE_FLOOR = 2,       /* no ascent after a reset of H^-1: converged at the finite-difference noise floor */
+  CF_OPT_ITER_CAP = 3,
+  CF_OPT_NONFINITE_START = 4,   /* f of the start is not finite (set by the driver; the problem never moves) */
+  CF_OPT_NONFINITE_STENCIL = 5
+};
+enum cf_opt_flag { CF_OPT_NEED_RESET = 1, CF_OPT_HAS_PAIR = 2, CF_OPT_FRESH = 4, CF_OPT_HAS_STEP = 8 };
+typedef struct cf_opt_params {
+  int32_t ndim;                        /* 1 .. CF_OPT_MAX_NDIM */
+  int32_t n_free;                      /* 1 .. ndim */
+  int32_t free_idx[CF_OPT_MAX_NDIM];   /* ascending theta indices of the free coordinates */
+  double lo[CF_OPT_MAX_NDIM];
+  double width[CF_OPT_MAX_NDIM];       /* hi - lo > 0 */
+  double h;                            /* stencil step in u, (0, 0.01] */
+  double delta;                        /* margin of u, (0, 1e-3] */
+  double c1;                           /* Armijo constant, (0, 1) */
+  double gtol;                         /* convergence: max |projected g| <= gtol + gtol_rel |f| */
+  double gtol_rel;
+  int32_t n_trials;                    /* K, 1 .. CF_OPT_MAX_TRIALS */
+  int32_t max_iter;                    /* >= 1 */
+} cf_opt_params;
+typedef struct cf_opt_state {
+  double* u;       /* [B * ndim] */
+  double* f;       /* [B] */
+  double* g;       /* [B * 16] gradient at u (free slots) */
+  double* g_prev;  /* [B * 16] gradient before the last accepted step */
+  double* s;       /* [B * 16] last accepted step in u */
+  double* hinv;    /* [B * 256] */
+  double* d;       /* [B * 16] direction */
+  double* gnorm;   /* [B] max |projected g| */
+  int8_t* form;    /* [B * 16] stencil forms */
+  int32_t* status; /* [B] cf_opt_status */
+  int32_t* n_iter; /* [B] */
+  int32_t* flags;  /* [B] cf_opt_flag bits */
+} cf_opt_state;
+
+int cf_opt_starts(const cf_opt_params* params, int64_t n, const double* d_x0, uint64_t key, int32_t random, double* d_u,
+                  double* d_theta, void* hip_stream);
+int cf_opt_stencil(const cf_opt_params* params, const cf_opt_state* state, const int32_t* d_active, int64_t n_active,
+                   double* d_rows, void* hip_stream);
+int cf_opt_direction(const cf_opt_params* params, const cf_opt_state* state, const int32_t* d_active, int64_t n_active,
+                     const double* d_fs, double* d_trials, void* hip_stream);
+int cf_opt_accept(const cf_opt_params* params, const cf_opt_state* state, const int32_t* d_active, int64_t n_active,
+                  const double* d_ft, void* hip_stream);
+int cf_opt_compact(const int32_t* d_active, int64_t n_active, const int32_t* d_status, int32_t* d_next, int32_t* d_count,
+                   void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
