@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <string>
 #include <vector>
@@ -38,6 +39,7 @@ extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
 #define QSR_TPB 256
 #define QSR_WAVES (QSR_TPB / 64)
+#define QSR_MAX_DEVICES 64  // device ordinals whose dynamic-LDS allowance is remembered (cf_qsr_launch)
 
 __device__ __forceinline__ double qsr_slot(const cf_dev_slot& s, const double* th) { return s.idx >= 0 ? th[s.idx] * s.scale : s.fixed; }
 
@@ -380,7 +382,29 @@ void cf_qsr_set_outputs(cf_qsr_state* q, double* parts, double* mu_sn, double* m
 int cf_qsr_launch(const cf_qsr_state* q, const double* theta, int64_t W, double* delta, double* extra, int out_kind,
                   double* th_copy, hipStream_t st) {
   const size_t lds = (size_t)(1 + q->args.two_grids) * q->args.n_grid * sizeof(double);
+  // 8192 nodes are 64 KiB of dynamic LDS, 128 KiB with an SN grid of its own, next to about 1.2 KB of static LDS: at or past
+  // the 64 KiB a launch may take by default.  The first launch on a device whose table could come near that default (half of
+  // it: the scripts' 3000 nodes stay below and never pay for the call) raises the kernel's allowance, once, to the largest
+  // table cf_create_quasar accepts.  Per device: a handle may have replicas on several.  Two threads that race here both
+  // set the same value.
+  static std::atomic<bool> raised[QSR_MAX_DEVICES];
+  constexpr int max_lds = 2 * 8192 * (int)sizeof(double);
+  if (lds > 32 * 1024) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return cf_set_error(CF_ERR_HIP, "cf_qsr_launch: hipGetDevice failed");
+    if (dev >= QSR_MAX_DEVICES || !raised[dev].load(std::memory_order_acquire)) {
+      if (hipFuncSetAttribute((const void*)&qsr_walker_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds) != hipSuccess)
+        return cf_set_error(CF_ERR_HIP, "cf_qsr_launch: " + std::to_string(max_lds) + " bytes of dynamic LDS refused on device " +
+                                            std::to_string(dev));
+      if (dev < QSR_MAX_DEVICES) raised[dev].store(true, std::memory_order_release);
+    }
+  }
   hipLaunchKernelGGL(qsr_walker_kernel, dim3((unsigned)W), dim3(QSR_TPB), lds, st, q->args, theta, W, delta, extra,
                      out_kind != CF_OUT_CHI2 ? 1 : 0, th_copy, q->parts, q->mu_sn, q->mu_q, q->bao);
+  // a refused launch is this call's error: the kernels behind it would otherwise finish the evaluation on stale residuals
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess)
+    return cf_set_error(CF_ERR_HIP, std::string("cf_qsr_launch: qsr_walker_kernel (or an earlier HIP call of this thread): ") +
+                                        hipGetErrorString(err));
   return 0;
 }

@@ -46,18 +46,35 @@ def _quad(mu, a):
 
 
 # ---- 1. kernels against the restatement ------------------------------------------------------------------------------
-def test_kernels_against_the_restatement_on_random_states(pkg, opt):
+# (ndim, free, K, B, n_active): the shape the scripts use, then the ends of the ranges the C entry points accept -- one lane
+# live and one trial, all sixteen lanes live with ndim = 16 (lane c also writes trial coordinate c) and eight trials, a single
+# free coordinate in the last of sixteen, and more than 1024 active problems (the second pass of the compaction's chunk loop)
+KERNEL_SHAPES = [(5, [0, 2, 3, 4], 4, 64, 50), (1, [0], 1, 64, 64), (16, list(range(16)), 8, 200, 150), (16, [15], 2, 64, 33),
+                 (7, [1, 3, 5], 8, 3000, 2500)]
+
+
+@pytest.mark.parametrize("d,free,K,B,n_active", KERNEL_SHAPES,
+                         ids=["scripts_shape", "one_lane_one_trial", "sixteen_lanes", "last_of_sixteen", "two_compaction_passes"])
+def test_kernels_against_the_restatement_on_random_states(pkg, opt, d, free, K, B, n_active):
     L, lib = pkg._lib, pkg.lib()
     rng = np.random.default_rng(11)
-    B, d, free = 64, 5, [0, 2, 3, 4]
-    nf, K = len(free), 4
-    bounds = np.array([[-1.0, 2.0], [0.1, 0.7], [-9.0, 9.0], [50.0, 90.0], [-0.5, 0.5]])
+    nf = len(free)
+    if d == 5:
+        bounds = np.array([[-1.0, 2.0], [0.1, 0.7], [-9.0, 9.0], [50.0, 90.0], [-0.5, 0.5]])
+        mu_h, sc_h = [0.3, 0.4, 1.0, 70.0, 0.1], [0.5, 0.1, 3.0, 5.0, 0.2]
+    else:  # a generator of its own: the draws below are the same for every shape
+        r2 = np.random.default_rng(1100 + d)
+        lo = r2.uniform(-50.0, 50.0, d)
+        bounds = np.stack([lo, lo + r2.uniform(0.2, 40.0, d)], axis=1)
+        mu_h = list(bounds[:, 0] + r2.uniform(0.3, 0.7, d) * (bounds[:, 1] - bounds[:, 0]))
+        sc_h = list(r2.uniform(0.1, 0.4, d) * (bounds[:, 1] - bounds[:, 0]))
     p = opt._params(bounds, free, opt._options(1e-6, K, 1e-5, None, 50, 1e-4))
     rp = ref.Params(bounds, free=free, n_trials=K, gtol=1e-5, max_iter=50)
     st = opt._State(B, d, DEV)
     u = rng.uniform(ref.DELTA, 1 - ref.DELTA, (B, d))
-    u[:8, 0], u[8:16, 2], u[16:20, 3] = ref.DELTA, 1 - ref.DELTA, ref.DELTA + 1.5e-6  # faces and one-sided stencils
-    u[20:24, 4] = 1 - ref.DELTA - 0.5e-6
+    # faces and one-sided stencils, on free coordinates
+    u[:8, free[0]], u[8:16, free[1 % nf]], u[16:20, free[2 % nf]] = ref.DELTA, 1 - ref.DELTA, ref.DELTA + 1.5e-6
+    u[20:24, free[3 % nf]] = 1 - ref.DELTA - 0.5e-6
     st.u.copy_(torch.from_numpy(u))
     st.f.copy_(torch.from_numpy(rng.normal(-5.0, 2.0, B)))
     st.g_prev[:, :nf] = torch.from_numpy(rng.normal(size=(B, nf)) * 10)
@@ -70,14 +87,15 @@ def test_kernels_against_the_restatement_on_random_states(pkg, opt):
     flag_set = [L.CF_OPT_NEED_RESET, L.CF_OPT_HAS_PAIR | L.CF_OPT_HAS_STEP, L.CF_OPT_HAS_STEP,
                 L.CF_OPT_HAS_PAIR | L.CF_OPT_HAS_STEP | L.CF_OPT_FRESH, L.CF_OPT_NEED_RESET | L.CF_OPT_HAS_STEP]
     st.flags.copy_(torch.tensor([flag_set[b % len(flag_set)] for b in range(B)], dtype=torch.int32))
-    act = rng.permutation(B)[:50].astype(np.int32)
+    act = rng.permutation(B)[:n_active].astype(np.int32)
     dact = torch.from_numpy(act).to(DEV)
     n = act.size
     probs = []
+    f_h, gp_h, s_h, fl_h = st.f.cpu().numpy(), st.g_prev.cpu().numpy(), st.s.cpu().numpy(), st.flags.cpu().numpy()  # one copy each
     for b in range(B):
-        q = ref.Problem(rp, u[b], float(st.f[b]))
-        q.g_prev, q.s = st.g_prev[b, :nf].cpu().numpy().copy(), st.s[b, :nf].cpu().numpy().copy()
-        q.H, q.flags = hs[b, :nf, :nf].copy(), int(st.flags[b])
+        q = ref.Problem(rp, u[b], float(f_h[b]))
+        q.g_prev, q.s = gp_h[b, :nf].copy(), s_h[b, :nf].copy()
+        q.H, q.flags = hs[b, :nf, :nf].copy(), int(fl_h[b])
         probs.append(q)
     cs = st.c_struct()
     stream = torch.cuda.current_stream(DEV).cuda_stream
@@ -87,8 +105,8 @@ def test_kernels_against_the_restatement_on_random_states(pkg, opt):
     np.testing.assert_array_equal(rows.cpu().numpy(), want_rows)
     np.testing.assert_array_equal(st.form[torch.from_numpy(act).long().to(DEV), :nf].cpu().numpy(), np.array([probs[b].form for b in act]))
     # stencil values: a smooth function of the rows, with one non-finite value in two problems
-    mu = torch.tensor([0.3, 0.4, 1.0, 70.0, 0.1], dtype=torch.float64, device=DEV)
-    sc = torch.tensor([0.5, 0.1, 3.0, 5.0, 0.2], dtype=torch.float64, device=DEV)
+    mu = torch.tensor(mu_h, dtype=torch.float64, device=DEV)
+    sc = torch.tensor(sc_h, dtype=torch.float64, device=DEV)
     fs = -0.5 * (((rows - mu) / sc) ** 2).sum(1)
     fs[3], fs[2 * nf * 7 + 1] = math.nan, -math.inf
     trials = torch.empty((n * K, d), dtype=torch.float64, device=DEV)
@@ -99,7 +117,7 @@ def test_kernels_against_the_restatement_on_random_states(pkg, opt):
     ia = torch.from_numpy(act).long().to(DEV)
     g, hd, dd = st.g[ia, :nf].cpu().numpy(), st.hinv[ia, :nf, :nf].cpu().numpy(), st.d[ia, :nf].cpu().numpy()
     ok = np.array([probs[b].status == ref.RUNNING for b in act])
-    assert ok.sum() > 30 and (~ok).sum() >= 2
+    assert ok.sum() > 0.6 * n and (~ok).sum() >= 2  # (30 of the 50 of the first shape)
     for a, b in enumerate(act):
         q = probs[b]
         assert int(st.status[b]) == q.status and int(st.flags[b]) == q.flags, (a, b)
@@ -167,6 +185,47 @@ def nested_uniform(key, stream, counter):
     import nested_reference
 
     return nested_reference.uniform(key, stream, counter)
+
+
+def test_starts_kernel_with_sixteen_free_coordinates(pkg, opt):
+    """ndim = n_free = 16: every coordinate drawn from its own stream, bit for bit the restatement's generator."""
+    L, lib = pkg._lib, pkg.lib()
+    rng = np.random.default_rng(16)
+    lo = rng.uniform(-100.0, 100.0, 16)
+    bounds = np.stack([lo, lo + rng.uniform(1e-3, 50.0, 16)], axis=1)
+    p = opt._params(bounds, list(range(16)), opt._options(1e-6, 8, 1e-5, None, 10, 1e-4))
+    n = 1025
+    key = opt.opt_key(16)
+    u, th = opt._starts(p, np.zeros((n, 16)), key, L, lib)
+    u, th = u.cpu().numpy(), th.cpu().numpy()
+    for c in range(16):
+        want = ref.DELTA + nested_uniform(key, c, np.arange(n)) * (1.0 - 2.0 * ref.DELTA)
+        np.testing.assert_array_equal(u[:, c], want, err_msg=f"coordinate {c}")
+    np.testing.assert_array_equal(th, bounds[:, 0] + u * (bounds[:, 1] - bounds[:, 0]))
+    assert np.all((u >= ref.DELTA) & (u <= 1 - ref.DELTA))
+
+
+@pytest.mark.parametrize("n_active", [1, 63, 64, 65, 1023, 1024, 1025, 2048, 5000])
+@pytest.mark.parametrize("running", ["random", "all", "none"])
+def test_compact_kernel_against_numpy(pkg, opt, n_active, running):
+    """cf_opt_compact alone: the still-running entries of the active list in order and their number, for lists shorter and
+    longer than the kernel's 1024-entry chunk; `next` is written up to the count and no further."""
+    L, lib = pkg._lib, pkg.lib()
+    rng = np.random.default_rng(n_active)
+    B = 6000
+    status = {"random": rng.integers(0, 6, B), "all": np.zeros(B), "none": rng.integers(1, 6, B)}[running].astype(np.int32)
+    act = rng.permutation(B)[:n_active].astype(np.int32)
+    keep = act[status[act] == ref.RUNNING]
+    sentinel = -12345
+    nxt = torch.full((n_active + 64,), sentinel, dtype=torch.int32, device=DEV)
+    cnt = torch.full((2,), sentinel, dtype=torch.int32, device=DEV)
+    dact, dstatus = torch.from_numpy(act).to(DEV), torch.from_numpy(status).to(DEV)
+    L.check(lib.cf_opt_compact(dact.data_ptr(), n_active, dstatus.data_ptr(), nxt.data_ptr(), cnt.data_ptr(),
+                               torch.cuda.current_stream(DEV).cuda_stream))
+    got, count = nxt.cpu().numpy(), cnt.cpu().numpy()
+    assert count[0] == keep.size and count[1] == sentinel
+    np.testing.assert_array_equal(got[:keep.size], keep)
+    np.testing.assert_array_equal(got[keep.size:], np.full(n_active + 64 - keep.size, sentinel))
 
 
 # ---- 2. analytic problems --------------------------------------------------------------------------------------------
