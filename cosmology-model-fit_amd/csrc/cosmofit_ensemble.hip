@@ -495,6 +495,8 @@ extern "C" int cf_ens_kde_prepare(const double* d_all_pos, int64_t w_total, int3
   if (rc) return rc;
   if (!d_all_pos || !d_params || !d_wc) return cf_set_error(CF_ERR_INVALID, "cf_ens_kde_prepare: null argument");
   const int64_t nc = cf_ens_comp_count(split_key, n_splits, split, w_total);
+  if (nc <= ndim)  // the covariance of nc <= ndim points is singular: NaN factors, and a chain that never moves
+    return cf_set_error(CF_ERR_INVALID, "cf_ens_kde_prepare: the KDE move needs more than ndim walkers in the complementary set");
   hipLaunchKernelGGL(ens_kde_prepare_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, d_all_pos, nc, (int)ndim, (int)n_splits,
                      (int)split, split_key, d_params, d_wc);
   return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_ens_kde_prepare: launch failed");

@@ -445,6 +445,7 @@ int cf_selftest_pos_ops(const double* a, const double* b, int64_t n, double* out
  *     d_ids [cf_ens_active_count] global indices, d_local_idx = d_ids - shard_start.
  *   cf_ens_kde_prepare: Silverman-bandwidth Gaussian KDE of the complementary set: d_params [2 ndim^2 + 1] =
  *     {chol (lower), inv(chol)^T, log normalisation}, d_wc [cf_ens_comp_count * ndim] = whitened complementary positions.
+ *     CF_ERR_INVALID, before anything is launched, when cf_ens_comp_count <= ndim (the covariance would be singular).
  *   cf_ens_propose: kind 0 stretch (scale a), 1 differential evolution (gamma0 = 2.38 / sqrt(2 ndim), jitter de_sigma),
  *     2 KDE independence proposal; d_y [n_active * ndim], d_log_factor [n_active] = log Hastings factor.
  *   cf_ens_accept: accept with probability min(1, exp(log_factor + lp_new - lp_old)) (NaN never accepts); updates

@@ -174,6 +174,9 @@ def test_ensemble_entry_points_validate_their_arguments(pkg):
     p = lambda a: C.cast(a, C.c_void_p)
     with pytest.raises(pkg.CosmofitError, match="even number"):
         L.check(lib.cf_ens_kde_prepare(p(buf), 7, 4, 2, 0, 0, p(buf), p(buf), None))
+    for w_total, ndim, n_splits in ((8, 4, 2), (6, 5, 2), (32, 16, 2), (6, 4, 3), (24, 16, 3)):  # nc <= ndim: a singular covariance
+        with pytest.raises(pkg.CosmofitError, match="CF_ERR_INVALID.*more than ndim walkers in the complementary set"):
+            L.check(lib.cf_ens_kde_prepare(p(buf), w_total, ndim, n_splits, 0, 0, p(buf), p(buf), None))
     with pytest.raises(pkg.CosmofitError, match="ndim"):
         L.check(lib.cf_ens_propose(0, p(buf), 8, 17, 2, 0, 0, p(ids), 4, 1, 2.0, 1e-5, None, None, p(buf), p(buf), None))
     with pytest.raises(pkg.CosmofitError, match="n_splits"):
