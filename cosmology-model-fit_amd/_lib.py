@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COSMOFIT_LIB") or os.path.join(_HERE, "libcosmofit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-CF_ABI_VERSION = 8
+CF_ABI_VERSION = 9
 CF_P_NSLOTS = 15
 SLOTS = ("offset", "H0", "Om", "obh2", "och2", "w0", "wa", "v", "rd", "fcc", "lin", "v2", "v3", "s8", "fs8err")
 
@@ -93,6 +93,8 @@ class cf_ns_prior(C.Structure):
 
 
 CF_QSR_BAO_NONE, CF_QSR_BAO_QUAD = 0, 1
+
+CF_MARG_MAX_NDIM, CF_MARG_MAX_BINS, CF_MARG_MAX_PAIRS, CF_MARG_MAX_SEGMENTS, CF_MARG_NOT_COUNTED = 16, 128, 256, 65536, 255
 
 CF_OPT_MAX_NDIM, CF_OPT_MAX_TRIALS = 16, 8
 CF_OPT_RUNNING, CF_OPT_CONVERGED, CF_OPT_NOISE_FLOOR, CF_OPT_ITER_CAP, CF_OPT_NONFINITE_START, CF_OPT_NONFINITE_STENCIL = range(6)
@@ -176,6 +178,8 @@ EXPORTS = {
     "cf_chain_mean": (C.c_int, [_VP, _I64, _I64, _VP, _VP]),
     "cf_chain_lagsum": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _I32, _VP, _VP]),
     "cf_chain_acf_mean": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP]),
+    "cf_marg_bin": (C.c_int, [_VP, _I64, _I32, _VP, _I32, _VP, _VP]),
+    "cf_marg_hist": (C.c_int, [_VP, _VP, C.c_double, _I64, _I32, _I32, _VP, _I32, _VP, _VP, _I32, _VP]),
     "cf_ns_prior_draw": (C.c_int, [_VP, _I64, C.c_uint64, _VP, _VP, _VP]),
     "cf_ns_transform": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),
     "cf_ns_walk_start": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _I64, C.c_uint64, _VP, _VP, _VP, _VP]),

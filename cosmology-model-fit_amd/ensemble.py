@@ -411,6 +411,18 @@ class ShardedEnsemble:
 
         return chain_stats.percentile(self.get_chain(discard=discard, thin=thin, flat=True), q)
 
+    def marginals(self, discard: int = 0, thin: int = 1, **kw) -> dict:
+        """``marginals.corner_data(get_chain(discard, thin, flat=True), **kw)``: what the reference's
+        ``plot_corner_and_chains`` hands to ``corner.corner``, computed on the device (a dict of small numpy arrays)."""
+        from . import marginals
+
+        return marginals.corner_data(self.get_chain(discard=discard, thin=thin, flat=True), **kw)
+
+    def mean_path(self, discard: int = 0) -> torch.Tensor:
+        """The walker mean per stored step, [n, ndim] on the device: the black line of the reference's trace plot
+        (corner_plot.py:30)."""
+        return self.get_chain(discard=discard).mean(dim=1)
+
     def full_state(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(positions [W_total, ndim], log-prob [W_total]) gathered on every rank (for tests / check-pointing)."""
         pos = self.gather_positions()

@@ -235,6 +235,7 @@ class DeviceNestedSampler:
         self._ln_x, self._it, self._n_like, self._n_walk_props = 0.0, 0, 0, 0
         self.n_nonfinite_start = 0
         self._results = None
+        self._post_dev = None  # (the results they belong to, points, weights) on the device, for marginals() / mean_std()
 
     # ---- device steps --------------------------------------------------------------------------------------------
     def _stream(self):
@@ -344,6 +345,34 @@ class DeviceNestedSampler:
         theta, ln_w, log_l, s = self._final()
         keep = ln_w > -math.inf
         return theta[keep], ln_w[keep] - s["log_z"], log_l[keep]
+
+    def _posterior_on_device(self):
+        """(points [N, ndim], weights [N] = exp(log_w)) of ``posterior()`` as float64 tensors on the sampler's device, uploaded
+        once per run (``run()`` drops the results they belong to)."""
+        import torch
+
+        self._final()
+        if self._post_dev is None or self._post_dev[0] is not self._results:
+            theta, log_w, _ = self.posterior()
+            self._post_dev = (self._results, torch.from_numpy(np.ascontiguousarray(theta)).to(self.device),
+                              torch.from_numpy(np.exp(log_w)).to(self.device))
+        return self._post_dev[1], self._post_dev[2]
+
+    def marginals(self, **kw) -> dict:
+        """``marginals.corner_data`` of the posterior points with weights exp(log_w): the numbers behind the weighted
+        triangle plot of the nautilus scripts."""
+        from . import marginals
+
+        pts, w = self._posterior_on_device()
+        return marginals.corner_data(pts, weights=w, **kw)
+
+    def mean_std(self):
+        """``marginals.weighted_mean_std`` of the same points and weights: (mean [ndim], std [ndim]) on the device, what the
+        nautilus scripts print per parameter (getdist's ``mean`` and ``std``)."""
+        from . import marginals
+
+        pts, w = self._posterior_on_device()
+        return marginals.weighted_mean_std(pts, w)
 
     @property
     def log_z(self) -> float:

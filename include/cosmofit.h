@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CF_ABI_VERSION 8
+#define CF_ABI_VERSION 9
 
 typedef struct cf_handle cf_handle;
 
@@ -488,6 +488,34 @@ int cf_chain_lagsum(const double* d_x, const double* d_mean, int64_t n_t, int64_
                     double* d_out, void* hip_stream);
 int cf_chain_acf_mean(const double* d_lagsum, const double* d_c0, int64_t n_w, int32_t ndim, int32_t nlag, double* d_f,
                       void* hip_stream);
+
+/* ---- marginals (csrc/cosmofit_marginals.hip): the histograms behind a corner plot ------------------------------------------
+ * Samples are [n, ndim] float64 in device memory, row-major and contiguous (a flat chain, or weighted posterior points).
+ * Limits of both entries: 1 <= n <= 2^31 - 1, 1 <= ndim <= CF_MARG_MAX_NDIM, 1 <= nbins <= CF_MARG_MAX_BINS; anything else
+ * returns CF_ERR_INVALID before anything is launched.
+ *   cf_marg_bin: d_idx [n * ndim] uint8 = numpy's bin of every value in its column's edges, d_edges [ndim * (nbins + 1)]
+ *     float64 in device memory (made on the host by np.linspace(lo, hi, nbins + 1) per column and uploaded, so that they have
+ *     numpy's bits; increasing).  Bin i iff edges[i] <= x < edges[i + 1]; the last bin also takes x == edges[nbins]; every
+ *     other value (below, above, NaN, +-inf) gets CF_MARG_NOT_COUNTED.  This is np.histogram's and np.histogram2d's rule,
+ *     reproduced exactly: the bin is guessed with one multiply and corrected by comparisons with the edges themselves.
+ *   cf_marg_hist: from d_idx, the ndim 1-D histograms d_h1 [ndim * nbins] and, for the host list pairs [npairs * 2]
+ *     (0 <= npairs <= CF_MARG_MAX_PAIRS, columns in 0 .. ndim - 1, repeats allowed), the 2-D histograms d_h2
+ *     [npairs * nbins * nbins]: H[p][i][j] = rows with column pairs[2p] in bin i and column pairs[2p + 1] in bin j
+ *     (np.histogram2d's orientation); a row counts if both indices are < nbins.  d_h2 may be null if npairs = 0.
+ *     d_w = null: int64 counts.  d_w [n] (weights >= 0, finite; w_max = their maximum > 0, both checked by the caller):
+ *     int64 fixed-point sums of q = rint(w / w_max * 2^s), s = 62 - ceil(log2 n), so that no sum can overflow; the caller
+ *     multiplies by w_max / 2^s.  All sums are integer sums (LDS and global integer atomics): the same input gives the same
+ *     bits on every run, for every n_segments and for every order of the rows.  n_segments (0 .. CF_MARG_MAX_SEGMENTS) is
+ *     the number of row segments the work is cut into, one workgroup per (pair, segment); 0 lets the library choose. */
+#define CF_MARG_MAX_NDIM 16
+#define CF_MARG_MAX_BINS 128
+#define CF_MARG_MAX_PAIRS 256
+#define CF_MARG_MAX_SEGMENTS 65536
+#define CF_MARG_NOT_COUNTED 255
+int cf_marg_bin(const double* d_x, int64_t n, int32_t ndim, const double* d_edges, int32_t nbins, uint8_t* d_idx,
+                void* hip_stream);
+int cf_marg_hist(const uint8_t* d_idx, const double* d_w, double w_max, int64_t n, int32_t ndim, int32_t nbins,
+                 const int32_t* pairs, int32_t npairs, int64_t* d_h1, int64_t* d_h2, int32_t n_segments, void* hip_stream);
 
 /* ---- nested sampling (csrc/cosmofit_nested.hip; the driver is cosmology-model-fit_amd/nested.py) -------------------------
  * Classic nested sampling with batch deletion on a device-resident live set: the per-step work of the constrained
