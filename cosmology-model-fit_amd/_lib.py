@@ -125,6 +125,19 @@ class cf_qsr_ext(C.Structure):
     ]
 
 
+CF_DQ_MAX, CF_CURVE_MAX_NZ = 32, 4096
+# cf_derived_code / cf_curve_code of include/cosmofit.h by the names derived.Spec takes
+DERIVED_CODES = {"H0": 0, "h": 1, "Om": 2, "omh2": 3, "obh2": 4, "och2": 5, "w0": 6, "wa": 7, "q0": 8, "j0": 9, "S8": 10, "rd": 11,
+                 "z_star": 12, "r_drag": 13, "z_drag": 14, "z_eq": 15, "H@": 16,
+                 "rs_star": 32, "DM_star": 33, "theta_star100": 34, "R": 35, "lA": 36}
+CURVE_CODES = {"H": 0, "DM": 1, "DV_rd": 2, "DM_rd": 3, "DH_rd": 4, "F_AP": 5, "mu": 6}
+
+
+class cf_derived_consts(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("has_rdrag_fit", C.c_int32), ("zdrag_fit", C.c_double * 10),
+                ("rdrag_fit", C.c_double * 11), ("zeq_or_h2", C.c_double)]
+
+
 class cf_info(C.Structure):
     _fields_ = [
         ("n_sn", C.c_int64), ("n_sn_pad", C.c_int64), ("packed_chol_bytes", C.c_int64),
@@ -193,6 +206,10 @@ EXPORTS = {
     "cf_opt_direction": (C.c_int, [C.POINTER(cf_opt_params), C.POINTER(cf_opt_state), _VP, _I64, _VP, _VP, _VP]),
     "cf_opt_accept": (C.c_int, [C.POINTER(cf_opt_params), C.POINTER(cf_opt_state), _VP, _I64, _VP, _VP]),
     "cf_opt_compact": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP]),
+    "cf_derived_device": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "cf_curves_device": (C.c_int, [_VP, _VP, _I64, _I32, _VP, _I32, _VP, _VP]),
+    "cf_derived": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I32, _VP, _VP]),
+    "cf_curves": (C.c_int, [_VP, _VP, _I64, _I32, _VP, _I32, _VP]),
 }
 
 

@@ -47,8 +47,21 @@ def _neutrino(omnu_denominator, N_EFF=N_EFF):
                 o_gamma_h2=O_GAMMA_H2)
 
 
-def _compression(priors, covariance, omnu_den, zstar_sbm, rdrag_bm, mode, n_eff=N_EFF):
+# z_drag amplitudes / exponents common to the compressions (cmb/data_planck_act_compression.py:136-138):
+# (1 + s1 c1 wb^e1 wm^e2 + s2 c2 wm^e3) wm^e4
+ZDRAG_CONSTS = (428.169, 0.256459, 0.616388, 925.56, 0.751615, -0.714129)
+
+
+def omega_r_h2(n_eff=N_EFF):
+    """``Omega_r_h2(Neff)`` of the compressions (cmb/data_planck_act_compression.py:39-40): the z_eq of cmb/cmb.py:135 takes
+    it at the full N_eff."""
+    return O_GAMMA_H2 * (1 + n_eff * (7 / 8) * (4 / 11) ** (4 / 3))
+
+
+def _compression(priors, covariance, omnu_den, zstar_sbm, rdrag_bm, mode, n_eff=N_EFF, zdrag_sbm=None):
     d = _neutrino(omnu_den, n_eff)
+    if zdrag_sbm is not None:
+        d.update(zdrag_fit=tuple(zdrag_sbm) + ZDRAG_CONSTS, zeq_or_h2=omega_r_h2(n_eff))
     d.update(cmb_prior=np.array(priors), cmb_cov=np.array(covariance), cmb_inv_cov=np.linalg.inv(np.array(covariance)),
              zstar_fit=tuple(zstar_sbm), rd_fit=tuple(rdrag_bm) + RDRAG_A, cmb_mode=mode)
     return d
@@ -60,14 +73,16 @@ PLANCK_ACT = _compression(
     [[1.54911112e-05, 1.03997132e-04, -2.10953275e-07],
      [1.03997132e-04, 5.43880523e-03, -1.53612827e-06],
      [-2.10953275e-07, -1.53612827e-06, 1.23574770e-08]],
-    94.0641, (0.70130133, 1.00839438, 1.02468387, 1.18438972), (0.99625075, 1.00593295), 1)
+    94.0641, (0.70130133, 1.00839438, 1.02468387, 1.18438972), (0.99625075, 1.00593295), 1,
+    zdrag_sbm=(1.00791144, 1.00585853, 1.05510863, 0.84044899))  # :131
 
 EARLY_LCDM = _compression(
     [0.010410274, 0.02223, 0.14208],
     1e-9 * np.array([[0.00662099420, 0.124442058, -1.19287532],
                      [0.124442058, 21.3441666, -94.0008323],
                      [-1.19287532, -94.0008323, 1488.41714]]),
-    94.07, (0.75717491, 1.00737989, 1.02737182, 1.20432292), (1.00140649, 1.00072621), 3)
+    94.07, (0.75717491, 1.00737989, 1.02737182, 1.20432292), (1.00140649, 1.00072621), 3,
+    zdrag_sbm=(1.00329735, 0.99968141, 1.00232108, 0.9893333))  # cmb/data_early_lcdm_compression.py:128
 
 # cmb/data_planck_compression.py:12-33,87,103 (Planck 2018 (R, l_A, omega_b), N_eff = 3.046)
 PLANCK = _compression(
@@ -75,7 +90,8 @@ PLANCK = _compression(
     [[2.09107356e-05, 1.78419597e-04, -4.46283183e-07],
      [1.78419597e-04, 7.81249750e-03, -4.24834772e-06],
      [-4.46283183e-07, -4.24834772e-06, 2.21402189e-08]],
-    94.07, (0.73491615, 1.00820929, 1.01709662, 1.17030559), (1.00078696, 1.00128548), 1, n_eff=3.046)
+    94.07, (0.73491615, 1.00820929, 1.01709662, 1.17030559), (1.00078696, 1.00128548), 1, n_eff=3.046,
+    zdrag_sbm=(1.00044649, 1.00006975, 1.00041899, 1.00135313))  # cmb/data_planck_compression.py:128
 
 BBN_SCHONEBERG = (0.02218, 0.00055)  # omega_b mean, sigma: y2024BBN/prior_lcdm_schoneberg.py:2-3
 

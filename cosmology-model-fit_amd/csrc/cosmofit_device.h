@@ -206,6 +206,21 @@ struct cf_qsr_args {
   const int32_t* bao_zi;  // [n_bao] distinct-redshift table of datum k
 };
 
+// Derived parameters of posterior samples (cosmofit_derived.hip): the request of one cf_derived_device call.  `need` says which
+// of the shared intermediates (fitting formulae, Gauss-Legendre integrals) any requested quantity reads.
+#define CF_DQ_MAX_D 32
+#define CF_DQ_NEED_ZSTAR 1
+#define CF_DQ_NEED_RDFIT 2
+#define CF_DQ_NEED_ZDRAG 4
+#define CF_DQ_NEED_GL 8
+struct cf_derived_kargs {
+  int32_t n_q, need;
+  int32_t codes[CF_DQ_MAX_D];
+  double args[CF_DQ_MAX_D];
+  double zdrag_fit[10];  // s1, s2, b, m, c1, e1, e2, c2, e3, e4
+  double rdrag_fit[11];  // b, m, a1..a9: the handle's rd_fit, or the caller's
+};
+
 #ifdef __HIPCC__
 typedef double cf_d2 __attribute__((ext_vector_type(2)));
 #else

@@ -46,6 +46,25 @@ def solve_mode_of(solve="auto", latency_mode=None) -> int:
     return L.SOLVE_MODES[solve]
 
 
+def _default_param(name: str) -> Param:
+    """A slot the caller does not name: w0 = -1, the two error-rescale factors 1, everything else unused (fixed 0)."""
+    return Param(fixed=-1.0) if name == "w0" else (Param(fixed=1.0) if name in ("fcc", "fs8err") else Param())
+
+
+def model_info(*, ndim, params, ez_model=L.CF_EZ_LATE_FLAT, fde=L.CF_FDE_LCDM, om_mode=0, n_grid=4000, bao=None, cmb=None,
+               quasar=None, devices=None, **_) -> dict:
+    """What ``derived.Spec`` validates its names against, from the keyword arguments of ``LikelihoodEngine`` (pure host
+    arithmetic: the same rules as cf_derived_device, before any device work).  slots: the filled ones (a theta index, or a
+    non-zero constant)."""
+    filled = {name for name in L.SLOTS
+              if params.get(name, _default_param(name)).idx >= 0 or params.get(name, _default_param(name)).fixed != 0.0}
+    bao = bao or {}
+    return dict(ndim=int(ndim), ez_model=int(ez_model), fde=int(fde), om_mode=int(om_mode), n_grid=int(n_grid), slots=filled,
+                rd_fit=bao.get("rd_fit") is not None, rd_wm_late=bao.get("rd_fit") is not None and bool(bao.get("rd_wm_late", False)),
+                dh_exact=bool(bao.get("dh_exact", False)), cmb=cmb is not None, quasar=quasar is not None,
+                multi_device=devices is not None)
+
+
 class LikelihoodEngine:
     def __init__(self, *, ndim: int, z_max: float, n_grid: int = 4000, fde: int = L.CF_FDE_LCDM,
                  ez_model: int = L.CF_EZ_LATE_FLAT, params: dict, sn: Optional[dict] = None,
@@ -112,7 +131,7 @@ class LikelihoodEngine:
         if unknown:
             raise ValueError(f"unknown parameter slots {sorted(unknown)}; valid: {L.SLOTS}")
         for i, name in enumerate(L.SLOTS):
-            p = params.get(name, Param(fixed=-1.0) if name == "w0" else (Param(fixed=1.0) if name in ("fcc", "fs8err") else Param()))
+            p = params.get(name, _default_param(name))
             d.param[i].idx, d.param[i].scale, d.param[i].fixed = p.idx, p.scale, p.fixed
         keep = []
         if sn is not None:
@@ -204,6 +223,8 @@ class LikelihoodEngine:
         self.ndim = ndim
         self.n_grid, self.z_max = int(n_grid), float(z_max)
         self.n_sn = int(d.n_sn)
+        self.model_info = model_info(ndim=ndim, params=params, ez_model=ez_model, fde=fde, om_mode=om_mode, n_grid=n_grid, bao=bao,
+                                     cmb=cmb, quasar=quasar, devices=devices)
         self._h = C.c_void_p()
         self._cf_eval = lib.cf_eval
         self.n_qsr = 0
@@ -379,6 +400,15 @@ class LikelihoodEngine:
         out = np.empty(z.size)
         L.check(L.lib().cf_eval_fs8_at(self._h, _ptr(th), _ptr(z), z.size, _ptr(out)))
         return out
+
+    def derived(self, theta, names, **consts):
+        """Derived parameters of one theta or a (host) batch [W, ndim] -> float64 [n_q] / [W, n_q]: ``derived.Spec(self, names,
+        **consts)`` evaluated through the host-buffer entry ``cf_derived`` (the device path is ``derived.columns``)."""
+        from . import derived as D
+
+        th = _f64(theta)
+        out = D.Spec(self, names, **consts).host_columns(np.atleast_2d(th))
+        return out[0] if th.ndim == 1 else out
 
     def enable_timing(self, slots=1, stride=1):
         """Keep HIP-event timings of the last `slots` timed evaluations (0 = off); only every `stride`-th evaluation is timed."""

@@ -181,12 +181,14 @@ class NativeMoves:
 class ShardedEnsemble:
     def __init__(self, log_prob_fn: Callable[[torch.Tensor], torch.Tensor], positions: torch.Tensor, *,
                  seed: int = 42, a: float = 2.0, moves=STRETCH_ONLY, de_sigma: float = 1e-5, group=None,
-                 randomize_split: bool = True, de_splits: int = 3, moves_impl=None):
+                 randomize_split: bool = True, de_splits: int = 3, moves_impl=None, blobs=None):
         """positions: [W_total, ndim] float64 initial ensemble, identical on every rank (it is sliced here).
         moves: sequence of (name, weight), name in {"stretch", "de", "kde"}; one is drawn per step.
         randomize_split: re-draw the splits every step (a random permutation per group of walkers); any shard boundaries.
         de_splits: sets of a DE step: 3 = emcee's DEMove (default), 2 = two halves like the other moves.
-        moves_impl: None = the library's kernels (positions must live on a GPU); tests pass the tensor statement."""
+        moves_impl: None = the library's kernels (positions must live on a GPU); tests pass the tensor statement.
+        blobs: a ``derived.Spec`` of the likelihood's engine: what ``get_blobs`` returns for the stored chain (emcee's blobs,
+            cmb/cmb.py:45-63,105)."""
         names = set(_KIND)
         if not moves or any(m not in names or w <= 0 for m, w in moves):
             raise ValueError(f"moves must be a non-empty sequence of (name in {sorted(names)}, weight > 0)")
@@ -230,6 +232,7 @@ class ShardedEnsemble:
         self._iteration = 0
         self._walker_acc = torch.zeros(self.stop - self.start, dtype=torch.int64, device=self.x.device)
         self._mcmc_steps = 0
+        self._blobs = blobs
         if moves_impl is None:
             if not self.x.is_cuda:
                 raise RuntimeError("ShardedEnsemble runs its moves in the library's HIP kernels: the positions must be on an "
@@ -378,6 +381,20 @@ class ShardedEnsemble:
     def get_log_prob(self, discard: int = 0, thin: int = 1, flat: bool = False) -> torch.Tensor:
         """emcee's ``get_log_prob``: the stored log P, [n, W_total] (flat: [n * W_total])."""
         return self._stored(self._chain_logp, discard, thin, flat)
+
+    def get_blobs(self, discard: int = 0, thin: int = 1, flat: bool = False) -> torch.Tensor:
+        """emcee's ``get_blobs``: the quantities of the ``blobs`` spec at the stored positions, [n, W_total, n_q] (flat:
+        [n * W_total, n_q]) with ``get_chain``'s slicing, on the ensemble's device, the same on every rank.  A blob is a function
+        of the stored position, so ``derived.columns`` of the stored chain is what recording at acceptance would have kept;
+        it is computed on demand and the step loop records nothing more."""
+        if self._blobs is None:
+            raise AttributeError("this ensemble has no blobs: pass blobs=derived.Spec(engine, names) to ShardedEnsemble")
+        from . import derived
+
+        chain = self.get_chain(discard=discard, thin=thin)
+        n, w, k = chain.shape
+        cols = derived.columns(self._blobs, chain.reshape(n * w, k))
+        return cols if flat else cols.reshape(n, w, cols.shape[1])
 
     def walker_acceptance_fraction(self) -> torch.Tensor:
         """Per-walker accepted / steps made under run_mcmc, [W_total] float64 on the device: emcee's

@@ -81,6 +81,15 @@ class _Base:
     def cmb_distances(self, params):
         return self.engine.parts(params)["cmb_vector"][0]
 
+    def derived(self, params, names, **consts):
+        """Derived parameters of one theta or a batch, [n_q] / [W, n_q]: the columns the post-fit blocks add to their samples
+        (bao/desi_cmb.py:196-199, bao/desi_cmb_union3_fs8.py:282-287, cmb/cmb.py:118-138), by the kernels of
+        ``derived.columns`` through host buffers.  names / consts: ``derived.Spec``; a mirror that keeps its compression
+        (``self.comp``) passes it as the default ``comp``."""
+        if "comp" not in consts and getattr(self, "comp", None) is not None:
+            consts["comp"] = self.comp
+        return self.engine.derived(params, names, **consts)
+
     def DM_z(self, z, params):
         """``DM_z(z, params)`` of the joint scripts (bao/desi_cmb_des5y.py:60-66 + interp_hermite): comoving distance at
         arbitrary redshifts from the walker's table (GPU) and the GPU Hermite operator."""

@@ -358,13 +358,26 @@ class DeviceNestedSampler:
                               torch.from_numpy(np.exp(log_w)).to(self.device))
         return self._post_dev[1], self._post_dev[2]
 
-    def marginals(self, **kw) -> dict:
+    def marginals(self, derived=None, **kw) -> dict:
         """``marginals.corner_data`` of the posterior points with weights exp(log_w): the numbers behind the weighted
-        triangle plot of the nautilus scripts."""
+        triangle plot of the nautilus scripts.  derived: a ``derived.Spec`` whose columns are appended to the sampled ones
+        (``derived.augment``) -- the S8 / q0 / j0 / r_d columns of bao/desi_cmb_union3_fs8.py:282-294."""
         from . import marginals
 
         pts, w = self._posterior_on_device()
+        if derived is not None:
+            from . import derived as D
+
+            pts = D.augment(derived, pts)
         return marginals.corner_data(pts, weights=w, **kw)
+
+    def posterior_derived(self, spec):
+        """(columns [N, n_q], weights [N]) on the sampler's device: ``derived.columns`` of the points of ``posterior()`` beside
+        their weights exp(log_w), for ``marginals._weighted_quantile`` / ``weighted_mean_std`` / ``corner_data``."""
+        from . import derived as D
+
+        pts, w = self._posterior_on_device()
+        return D.columns(spec, pts), w
 
     def mean_std(self):
         """``marginals.weighted_mean_std`` of the same points and weights: (mean [ndim], std [ndim]) on the device, what the

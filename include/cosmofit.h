@@ -677,6 +677,81 @@ int cf_opt_accept(const cf_opt_params* params, const cf_opt_state* state, const 
 int cf_opt_compact(const int32_t* d_active, int64_t n_active, const int32_t* d_status, int32_t* d_next, int32_t* d_count,
                    void* hip_stream);
 
+/* ---- derived parameters and prediction curves of posterior samples (csrc/cosmofit_derived.hip; the driver is
+ * cosmology-model-fit_amd/derived.py) -----------------------------------------------------------------------------------------
+ * What the post-fit blocks of the scripts do first with their samples: add columns.  Rows are d_theta [S * ndim] float64,
+ * row-major, in device memory on the handle's device (a flat chain, or the weighted nested posterior); the model, the slot
+ * mapping (cf_param, om_mode, rd_mode, rd_wm_mode), the fit coefficients, the Gauss-Legendre nodes and the neutrino constants
+ * are the handle's.  One thread per row for the scalar quantities, one workgroup (and one distance table in LDS) per row for
+ * the curves; every sum runs in a fixed order, so a row's values depend neither on S, nor on the row's position, nor on the
+ * launch geometry.  A non-finite theta entry gives NaN in the columns that read it and touches no other row; there is no box
+ * check.  A quantity whose slot or block the handle lacks is CF_ERR_INVALID with the quantity's name in the message.
+ *
+ * Scalar quantities (cf_derived_code, one `arg` each, 0 unless stated).  With h = H0 / 100, wb / wc = slots CF_P_OBH2 /
+ * CF_P_OCH2, wnu = cf_desc.omnu_h2:
+ *   CF_DQ_H0, CF_DQ_H          slot CF_P_H0, and H0 / 100
+ *   CF_DQ_OM                   CF_EZ_PHYSICAL: (wb + wc + wnu) / h^2                       bao/desi_cmb.py:196-197
+ *                              CF_EZ_LATE_FLAT: slot CF_P_OM, or slot / h^2 with om_mode = 1  bao/desi_omh2.py:18-20
+ *   CF_DQ_OMH2                 wb + wc + wnu, or Omega_m h^2                               bao/desi_cmb.py:196, bao/desi_union3_bbn.py:175
+ *   CF_DQ_OBH2, CF_DQ_OCH2     the slots
+ *   CF_DQ_W0, CF_DQ_WA         the slots; CF_FDE_THAWING: wa = -1.5 (1 - w0^2)             bao/desi_union3_bbn.py:320
+ *   CF_DQ_Q0                   Om / 2 + (1 + 3 w0) (1 - Om) / 2                            bao/desi_cmb_union3_fs8.py:238-240
+ *   CF_DQ_J0                   1 + 1.5 (1 - Om) (3 w0 (1 + w0) + wa)                       bao/desi_cmb_union3_fs8.py:243-245
+ *   CF_DQ_S8                   sigma_8 (Om / 0.3)^0.5, sigma_8 = slot CF_P_S8              bao/desi_cmb_union3_fs8.py:284
+ *   CF_DQ_RD                   what the BAO block divides by: slot CF_P_RD, or the r_drag fit (CF_RD_FIT)  bao/desi_cmb.py:81-82
+ *   CF_DQ_Z_STAR               z_star(wb, wb + wc + wnu), cf_desc.zstar_fit                cmb/data_planck_act_compression.py:86-99
+ *   CF_DQ_R_DRAG               r_drag(wb, wm): cf_desc.rd_fit (CF_RD_FIT) or cf_derived_consts.rdrag_fit   cmb/...:102-124
+ *   CF_DQ_Z_DRAG               z_drag(wb, wm), cf_derived_consts.zdrag_fit                 cmb/data_planck_act_compression.py:127-138
+ *                              (wm of both: wb + wc + wnu, or Omega_m h^2 with rd_wm_mode = 1, bao/desi_bbn.py:46-60)
+ *   CF_DQ_Z_EQ                 -1 + (wb + wc) / arg, arg = Omega_r h^2 (0: cf_derived_consts.zeq_or_h2)   cmb/cmb.py:134-137
+ *   CF_DQ_H_AT                 H(arg) in km/s/Mpc, arg = z                                 ohd/cc.py:95-96
+ * Gauss-Legendre quantities (the handle has a compressed-CMB block, hence nodes): the integrands, the node order and the z*
+ * of cmb_distances, cmb/data_planck_act_compression.py:160-212
+ *   CF_DQ_RS_STAR              r_s(z*) in Mpc                                              :183-197
+ *   CF_DQ_DM_STAR              D_M(z*) in Mpc                                              :160-172
+ *   CF_DQ_THETA_STAR100        100 r_s(z*) / D_M(z*)                                       cmb/cmb.py:56,63
+ *   CF_DQ_R                    100 sqrt(wb + wc + wnu) D_M(z*) / c                         :210
+ *   CF_DQ_LA                   pi D_M(z*) / r_s(z*)                                        :211
+ *
+ * Curves (cf_curve_code) at d_z [nz]: distances from the row's own n_grid-node trapezoid table and cubic Hermite with linear
+ * extrapolation beyond the grid (DM_z of the scripts, bao/desi_cmb.py:59-65), D_H by cf_desc.bao_dh_mode, r_d as CF_DQ_RD:
+ *   CF_CURVE_H  H(z)   CF_CURVE_DM  D_M(z)   CF_CURVE_DV_RD / _DM_RD / _DH_RD / _FAP  bao_theory(z, qty, params) (bao/desi.py:38-56)
+ *   CF_CURVE_MU  25 + 5 log10((1 + z) D_M(z))  (sn/pantheon.py:52-54)
+ * A non-finite z gives NaN.
+ *
+ * cf_derived_device / cf_curves_device: d_out [S * n_q] / [S * nz] float64, row-major; asynchronous on `hip_stream`, ordered
+ * like any other work on that stream (they use no workspace of the handle, so they are never the stream switch of
+ * cf_eval_device's contract and may be captured); a single-device handle; S = 0 is a no-op; 1 <= n_q <= CF_DQ_MAX,
+ * 1 <= nz <= CF_CURVE_MAX_NZ.  `consts` may be NULL when no requested quantity reads it.  cf_derived / cf_curves: the same on
+ * host buffers, synchronous. */
+#define CF_DQ_MAX 32
+#define CF_CURVE_MAX_NZ 4096
+enum cf_derived_code {
+  CF_DQ_H0 = 0, CF_DQ_H = 1, CF_DQ_OM = 2, CF_DQ_OMH2 = 3, CF_DQ_OBH2 = 4, CF_DQ_OCH2 = 5, CF_DQ_W0 = 6, CF_DQ_WA = 7,
+  CF_DQ_Q0 = 8, CF_DQ_J0 = 9, CF_DQ_S8 = 10, CF_DQ_RD = 11, CF_DQ_Z_STAR = 12, CF_DQ_R_DRAG = 13, CF_DQ_Z_DRAG = 14,
+  CF_DQ_Z_EQ = 15, CF_DQ_H_AT = 16,
+  CF_DQ_RS_STAR = 32, CF_DQ_DM_STAR = 33, CF_DQ_THETA_STAR100 = 34, CF_DQ_R = 35, CF_DQ_LA = 36
+};
+enum cf_curve_code {
+  CF_CURVE_H = 0, CF_CURVE_DM = 1, CF_CURVE_DV_RD = 2, CF_CURVE_DM_RD = 3, CF_CURVE_DH_RD = 4, CF_CURVE_FAP = 5, CF_CURVE_MU = 6
+};
+typedef struct cf_derived_consts {
+  int32_t struct_size;   /* sizeof(cf_derived_consts) as seen by the caller */
+  int32_t has_rdrag_fit; /* 1: rdrag_fit is set (only read by CF_DQ_R_DRAG on a handle without CF_RD_FIT) */
+  double zdrag_fit[10];  /* s1, s2, b, m, then c1, e1, e2, c2, e3, e4 of (1 + s1 c1 wb^e1 wm^e2 + s2 c2 wm^e3) wm^e4
+                            (wb, wm raised to b, m first)          cmb/data_planck_act_compression.py:127-138 */
+  double rdrag_fit[11];  /* b, m, a1..a9 as cf_desc.rd_fit */
+  double zeq_or_h2;      /* Omega_r h^2 of z_eq: cmb.Omega_r_h2(), N_eff = 3.044     cmb/cmb.py:135 */
+} cf_derived_consts;
+
+int cf_derived_device(cf_handle* h, const double* d_theta, int64_t S, const int32_t* codes, const double* args, int32_t n_q,
+                      const cf_derived_consts* consts, double* d_out, void* hip_stream);
+int cf_curves_device(cf_handle* h, const double* d_theta, int64_t S, int32_t code, const double* d_z, int32_t nz, double* d_out,
+                     void* hip_stream);
+int cf_derived(cf_handle* h, const double* theta, int64_t S, const int32_t* codes, const double* args, int32_t n_q,
+               const cf_derived_consts* consts, double* out);
+int cf_curves(cf_handle* h, const double* theta, int64_t S, int32_t code, const double* z, int32_t nz, double* out);
+
 #ifdef __cplusplus
 }
 #endif
