@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COSMOFIT_LIB") or os.path.join(_HERE, "libcosmofit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-CF_ABI_VERSION = 9
+CF_ABI_VERSION = 10
 CF_P_NSLOTS = 15
 SLOTS = ("offset", "H0", "Om", "obh2", "och2", "w0", "wa", "v", "rd", "fcc", "lin", "v2", "v3", "s8", "fs8err")
 
@@ -138,6 +138,19 @@ class cf_derived_consts(C.Structure):
                 ("rdrag_fit", C.c_double * 11), ("zeq_or_h2", C.c_double)]
 
 
+CF_GP_NDIM, CF_GP_MAX_N, CF_GP_MAX_NZ = 4, 64, 65536
+
+
+class cf_gp_desc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32), ("n", C.c_int32), ("_pad", C.c_int32),
+                ("z", C.c_void_p), ("y", C.c_void_p), ("cov", C.c_void_p), ("bounds", C.c_void_p)]
+
+
+class cf_gp_info(C.Structure):
+    _fields_ = [("n", C.c_int32), ("device", C.c_int32), ("ld", C.c_int32), ("lds_bytes", C.c_int32),
+                ("failed_factorizations", C.c_int64)]
+
+
 class cf_info(C.Structure):
     _fields_ = [
         ("n_sn", C.c_int64), ("n_sn_pad", C.c_int64), ("packed_chol_bytes", C.c_int64),
@@ -210,6 +223,13 @@ EXPORTS = {
     "cf_curves_device": (C.c_int, [_VP, _VP, _I64, _I32, _VP, _I32, _VP, _VP]),
     "cf_derived": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I32, _VP, _VP]),
     "cf_curves": (C.c_int, [_VP, _VP, _I64, _I32, _VP, _I32, _VP]),
+    "cf_gp_create": (C.c_int, [C.POINTER(cf_gp_desc), C.POINTER(_VP)]),
+    "cf_gp_destroy": (None, [_VP]),
+    "cf_gp_get_info": (C.c_int, [_VP, C.POINTER(cf_gp_info)]),
+    "cf_gp_mll_device": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP]),
+    "cf_gp_predict_device": (C.c_int, [_VP, _VP, _I64, _VP, _I32, C.c_double, _VP, _VP]),
+    "cf_gp_mll": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),
+    "cf_gp_predict": (C.c_int, [_VP, _VP, _I64, _VP, _I32, C.c_double, _VP]),
 }
 
 

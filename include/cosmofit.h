@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CF_ABI_VERSION 9
+#define CF_ABI_VERSION 10
 
 typedef struct cf_handle cf_handle;
 
@@ -751,6 +751,62 @@ int cf_curves_device(cf_handle* h, const double* d_theta, int64_t S, int32_t cod
 int cf_derived(cf_handle* h, const double* theta, int64_t S, const int32_t* codes, const double* args, int32_t n_q,
                const cf_derived_consts* consts, double* out);
 int cf_curves(cf_handle* h, const double* theta, int64_t S, int32_t code, const double* z, int32_t nz, double* out);
+
+/* ---- Gaussian-process reconstruction of H(z) (csrc/cosmofit_gp.hip; the driver is cosmology-model-fit_amd/gp.py) -------------
+ * The model of ohd/cc_gp.py:14-41 with ohd/gp_lib.py:55-68: data z [n], y [n], a symmetric covariance C [n, n]; hyperparameters
+ * theta = (m, s_f^2, l, s) = constant mean, output scale, length scale, noise scale, in natural form (a box replaces gpytorch's
+ * constraints):
+ *   K_ij = s_f^2 exp(-(z_i - z_j)^2 / (2 l^2)) + s C_ij,   r = y - m,   K = L L^T
+ *   log ML = -1/2 r^T K^-1 r - sum_i log L_ii - (n / 2) log 2 pi        (the whole marginal likelihood, not a per-datum loss)
+ * and at a test redshift z*, with k* = k(z, z*), dk* = d k(z, z*) / d z*, v = L^-1 k*, u = L^-1 dk*, w = L^-1 r:
+ *   [0] mean = m + v . w            [1] var = s_f^2 - v . v + s noise           (`noise`: test_noise of cc_gp.py:76-79)
+ *   [2] dmean = u . w               [3] dvar = s_f^2 / l^2 - u . u               [4] cov(value, derivative) = -v . u
+ * All arithmetic is float64 and the kernels work on whatever (y, C) they are given (gp.py normalises as the script does).
+ *
+ * cf_gp_create validates before its first HIP call (1 <= n <= CF_GP_MAX_N, non-null pointers, finite data, C symmetric to 1e-12
+ * relative, bounds [4][2] finite with lo < hi and lo >= 0 for s_f^2, l, s) and copies everything to the device.
+ *
+ * cf_gp_mll_device: d_theta [W * 4] -> d_out [W], and d_parts [W * 2] = (r^T K^-1 r, log|K|) when not NULL.  Asynchronous on
+ * `hip_stream`, one wave per row, K built and factored in LDS.  A row with an entry not strictly inside the box (NaN and +-inf
+ * included) is -inf without being evaluated (its parts are NaN); a pivot <= 0 or non-finite is -inf, NaN parts, and one count
+ * in cf_gp_info.failed_factorizations; the value is never NaN.
+ *
+ * cf_gp_predict_device: d_theta [S * 4], d_zstar [nz] -> d_out [S * nz * 5], the five quantities above.  One workgroup per row:
+ * factor once, then every test point.  A row outside the box or with a failed factorisation is NaN in that row only; a
+ * non-finite z* is NaN at that point only.  1 <= nz <= CF_GP_MAX_NZ, noise finite and >= 0.
+ *
+ * Every sum runs in index order: a row's bits depend neither on W / S, nor on the row's position, nor on the launch geometry.
+ * Zero rows is a no-op; up to 2^31 - 1 rows per call, launched as grids of at most 2^22 rows one after the other on the stream.
+ * cf_gp_mll / cf_gp_predict: the same on host buffers, synchronous. */
+#define CF_GP_NDIM 4
+#define CF_GP_MAX_N 64
+#define CF_GP_MAX_NZ 65536
+typedef struct cf_gp cf_gp;
+typedef struct cf_gp_desc {
+  int32_t struct_size; /* sizeof(cf_gp_desc) as seen by the caller */
+  int32_t device;
+  int32_t n;
+  int32_t _pad;
+  const double* z;      /* [n] */
+  const double* y;      /* [n] */
+  const double* cov;    /* [n * n] row-major */
+  const double* bounds; /* [4 * 2]: (lo, hi) of m, s_f^2, l, s */
+} cf_gp_desc;
+typedef struct cf_gp_info {
+  int32_t n, device;
+  int32_t ld;        /* leading dimension of K in LDS (doubles) */
+  int32_t lds_bytes; /* dynamic LDS of one row */
+  int64_t failed_factorizations; /* rows of cf_gp_mll_device / cf_gp_mll whose factorisation met a pivot <= 0 or non-finite */
+} cf_gp_info;
+
+int cf_gp_create(const cf_gp_desc* desc, cf_gp** out);
+void cf_gp_destroy(cf_gp* gp);
+int cf_gp_get_info(cf_gp* gp, cf_gp_info* info); /* waits for the device */
+int cf_gp_mll_device(cf_gp* gp, const double* d_theta, int64_t W, double* d_out, double* d_parts, void* hip_stream);
+int cf_gp_predict_device(cf_gp* gp, const double* d_theta, int64_t S, const double* d_zstar, int32_t nz, double noise,
+                         double* d_out, void* hip_stream);
+int cf_gp_mll(cf_gp* gp, const double* theta, int64_t W, double* out, double* parts);
+int cf_gp_predict(cf_gp* gp, const double* theta, int64_t S, const double* zstar, int32_t nz, double noise, double* out);
 
 #ifdef __cplusplus
 }
