@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COSMOFIT_LIB") or os.path.join(_HERE, "libcosmofit_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-CF_ABI_VERSION = 10
+CF_ABI_VERSION = 11
 CF_P_NSLOTS = 15
 SLOTS = ("offset", "H0", "Om", "obh2", "och2", "w0", "wa", "v", "rd", "fcc", "lin", "v2", "v3", "s8", "fs8err")
 
@@ -151,6 +151,28 @@ class cf_gp_info(C.Structure):
                 ("failed_factorizations", C.c_int64)]
 
 
+CF_FIELD_MAX_NQ, CF_FIELD_MAX_NDIM, CF_FIELD_NPAR, CF_FIELD_NSCALAR, CF_FIELD_LAUNCH_ROWS = 4096, 64, 4, 5, 1 << 22
+CF_FIELD_OK, CF_FIELD_PHANTOM, CF_FIELD_BAD = 0, 1, 2
+FIELD_PARS = ("H0", "Om", "w0", "wa")
+FIELD_SCALARS = ("phi_today", "t_today", "hubble_time", "phi_max", "t_max")
+FIELD_OUTPUTS = ("phi_a", "t_a", "w_a", "K_a", "V_a", "phi_grid", "a_phi", "V_phi", "t_grid", "a_t", "phi_t")
+
+
+class cf_field_desc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("fde", C.c_int32), ("n_a", C.c_int32), ("ndim", C.c_int32), ("n_par", C.c_int32),
+                ("_pad", C.c_int32), ("a_min", C.c_double), ("a_max", C.c_double), ("orh2", C.c_double),
+                ("par", cf_param * CF_FIELD_NPAR)]
+
+
+class cf_field_queries(C.Structure):
+    _fields_ = [("a_q", C.c_void_p), ("phi_q", C.c_void_p), ("t_q", C.c_void_p), ("n_aq", C.c_int32), ("n_phi", C.c_int32),
+                ("n_t", C.c_int32), ("_pad", C.c_int32)]
+
+
+class cf_field_out(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in FIELD_OUTPUTS + ("scalars", "status")]
+
+
 class cf_info(C.Structure):
     _fields_ = [
         ("n_sn", C.c_int64), ("n_sn_pad", C.c_int64), ("packed_chol_bytes", C.c_int64),
@@ -230,6 +252,10 @@ EXPORTS = {
     "cf_gp_predict_device": (C.c_int, [_VP, _VP, _I64, _VP, _I32, C.c_double, _VP, _VP]),
     "cf_gp_mll": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),
     "cf_gp_predict": (C.c_int, [_VP, _VP, _I64, _VP, _I32, C.c_double, _VP]),
+    "cf_field_launch_count": (_I64, [_I64]),
+    "cf_field_launch_range": (None, [_I64, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
+    "cf_field_device": (C.c_int, [C.POINTER(cf_field_desc), _VP, _I64, C.POINTER(cf_field_queries), C.POINTER(cf_field_out), _VP]),
+    "cf_field": (C.c_int, [C.POINTER(cf_field_desc), _VP, _I64, C.POINTER(cf_field_queries), C.POINTER(cf_field_out)]),
 }
 
 

@@ -292,6 +292,30 @@ def band_chunk(n: int, nz: int, max_bytes: int) -> int:
     return int(max(1, min(nz, L.CF_CURVE_MAX_NZ, max_bytes // (_BAND_BUFFERS * 8 * max(n, 1)))))
 
 
+def reduce_columns(block: torch.Tensor, qs: np.ndarray, w: Optional[torch.Tensor] = None, own_buffers: bool = False):
+    """(quantiles [len(qs), m], mean [m], std [m]) as numpy, of the columns of block [n, m], every column on its own: the
+    reduction of ``bands`` (and of ``quintessence.bands``).  own_buffers: every column is summed from an allocation of its
+    own.  torch's sum reads an unaligned head of its input apart, so the bits of a column's mean can depend on where the
+    column starts: in the transposed copy that is a multiple of n doubles, which for odd n depends on the column's place in the
+    chunk; in a buffer of its own it does not."""
+    n, m = block.shape
+    w_tot = None if w is None else w.sum()
+    if w is None:
+        out_b = _percentile(block, list(100.0 * qs)).cpu().numpy()
+    else:
+        out_b = _weighted_quantile(block, w, qs)
+    # mean and std column by column on contiguous copies: the order of each sum depends on n alone, not on the chunk's width
+    cols = block.t().contiguous()
+    means, stds = [], []
+    for j in range(m):
+        c = cols[j].clone() if own_buffers else cols[j]
+        mu = c.sum() / n if w is None else (w * c).sum() / w_tot
+        var = ((c - mu) ** 2).sum() / n if w is None else (w * (c - mu) ** 2).sum() / w_tot
+        means.append(mu)
+        stds.append(torch.sqrt(var))
+    return out_b, torch.stack(means).cpu().numpy(), torch.stack(stds).cpu().numpy()
+
+
 def bands(engine, samples: torch.Tensor, z, quantity: str, q=(0.159, 0.5, 0.841), weights: Optional[torch.Tensor] = None,
           max_bytes: int = 2**31) -> dict:
     """Posterior-predictive band of `quantity` over z: dict(z [nz], q [len(q)], bands [len(q), nz], mean [nz], std [nz]) as
@@ -313,24 +337,9 @@ def bands(engine, samples: torch.Tensor, z, quantity: str, q=(0.159, 0.5, 0.841)
         w = marginals._weights(weights, n, "bands")[0]
     step = band_chunk(n, zs.size, int(max_bytes))
     out_b, out_m, out_s = np.empty((qs.size, zs.size)), np.empty(zs.size), np.empty(zs.size)
-    w_tot = None if w is None else w.sum()
     for k0 in range(0, zs.size, step):
         block = curves(engine, samples, zs[k0:k0 + step], quantity)  # [n, m]
         m = block.shape[1]
-        if w is None:
-            out_b[:, k0:k0 + m] = _percentile(block, list(100.0 * qs)).cpu().numpy()
-        else:
-            out_b[:, k0:k0 + m] = _weighted_quantile(block, w, qs)
-        # mean and std column by column on contiguous copies: the order of each sum depends on n alone, not on the chunk's width
-        cols = block.t().contiguous()
-        means, stds = [], []
-        for j in range(m):
-            c = cols[j]
-            mu = c.sum() / n if w is None else (w * c).sum() / w_tot
-            var = ((c - mu) ** 2).sum() / n if w is None else (w * (c - mu) ** 2).sum() / w_tot
-            means.append(mu)
-            stds.append(torch.sqrt(var))
-        out_m[k0:k0 + m] = torch.stack(means).cpu().numpy()
-        out_s[k0:k0 + m] = torch.stack(stds).cpu().numpy()
-        del block, cols
+        out_b[:, k0:k0 + m], out_m[k0:k0 + m], out_s[k0:k0 + m] = reduce_columns(block, qs, w)
+        del block
     return dict(z=zs, q=qs, bands=out_b, mean=out_m, std=out_s)

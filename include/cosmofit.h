@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CF_ABI_VERSION 10
+#define CF_ABI_VERSION 11
 
 typedef struct cf_handle cf_handle;
 
@@ -807,6 +807,85 @@ int cf_gp_predict_device(cf_gp* gp, const double* d_theta, int64_t S, const doub
                          double* d_out, void* hip_stream);
 int cf_gp_mll(cf_gp* gp, const double* theta, int64_t W, double* out, double* parts);
 int cf_gp_predict(cf_gp* gp, const double* theta, int64_t S, const double* zstar, int32_t nz, double noise, double* out);
+
+/* ---- Quintessence reconstruction (csrc/cosmofit_field.hip; the driver is cosmology-model-fit_amd/quintessence.py) ------------
+ * field.py for every row of a chain.  On a = linspace(a_min, a_max, n_a), with h = H0 / 100, Or = orh2 / h^2 and
+ *   E^2(a) = Om a^-3 + Or a^-4 + (1 - Om - Or) rho_de(a)                                        field.py:23-26
+ *   CF_FDE_THAWING  1 + w = 2 (1 + w0) a^3 / D,  rho_de = 4 / D^2,  D = (1 + w0) a^3 + 1 - w0     :19-21
+ *   CF_FDE_WCDM     1 + w = 1 + w0,               rho_de = a^(-3 (1 + w0))
+ *   CF_FDE_CPL      1 + w = 1 + w0 + wa (1 - a),  rho_de = a^(-3 (1 + w0 + wa)) exp(-3 wa (1 - a))
+ * (CF_FDE_LCDM has no field and is refused) the row's tables are the cumulative trapezoids (scipy's, initial = 0)
+ *   phi(a) of sqrt((1 + w) rho_de) / (a H0 E)   :40-42      t(a) of 1 / (a E), times 9.77813 / h Gyr   :97-104
+ * 1 + w is formed directly, not as 1 + (-1 + x) as the script has it: below a ~ 0.01 the device values are the more accurate
+ * ones (the script's phi differs by up to 1.6e-6 relative at its first nodes, 4e-15 of the row's largest phi).
+ *
+ * Queries, each set optional, every output pointer optional (NULL: that part is skipped), outputs row-major [S, n]:
+ *   a_q [n_aq]     phi_a, t_a: np.interp on the a grid (clamped outside); w_a, K_a = (1 + w) rho_de / 2, V_a = (1 - w) rho_de / 2
+ *                  analytic at a_q                                                                :31-32,68,105
+ *   phi_q [n_phi]  a_phi = interp1d(phi, a, linear, extrapolate)(phi_q), V_phi = V(a_phi)            :44-48
+ *                  phi_q = NULL with n_phi >= 1: every row's own linspace(phi[0], phi[n_a - 1], n_phi), written to phi_grid
+ *   t_q [n_t]      a_t = interp1d(t, a, linear, extrapolate)(t_q), phi_t = np.interp(t_q, t, phi), t in Gyr   :108-114
+ *                  t_q = NULL with n_t >= 1: every row's own linspace(t[min(10, n_a - 1)], min(1.5 t_today, 0.95 t[n_a - 1]),
+ *                  n_t), written to t_grid
+ *   scalars [S, CF_FIELD_NSCALAR] (cf_field_scalar), status [S] (cf_field_status)
+ * A NaN query gives NaN at that point only.  Status of a row: CF_FIELD_OK; CF_FIELD_PHANTOM when 1 + w < 0 at a node (phi_a,
+ * phi_grid, a_phi, V_phi, phi_t, phi_today and phi_max are NaN, the rest is computed); CF_FIELD_BAD for a non-finite parameter,
+ * H0 <= 0, or E^2 <= 0 / non-finite at a node (everything is NaN).  A bad row never touches its neighbours.
+ *
+ * The parameters H0, Om, w0 and (CF_FDE_CPL only, n_par = 4, otherwise n_par = 3) wa come from theta[idx] * scale or are fixed.
+ * Validated before the first HIP call (CF_ERR_INVALID): struct_size, fde, 16 <= n_a <= 8192, finite 0 < a_min < 1 < a_max,
+ * orh2 finite >= 0, 1 <= ndim <= CF_FIELD_MAX_NDIM, columns < ndim, n_par, 0 <= S <= CF_FIELD_MAX_ROWS, at most
+ * CF_FIELD_MAX_NQ points per set, an output whose query set is empty.  S = 0 is a no-op.
+ *
+ * cf_field_device: one 512-thread workgroup per row (grids of at most CF_FIELD_LAUNCH_ROWS rows), the row's {phi, t} table in LDS (16 n_a + 8 KB); asynchronous on
+ * `hip_stream` on the current device, ordered like any other work on that stream, no workspace, may be captured.  Every sum
+ * runs in an order fixed by n_a alone: a row's bits depend neither on S, nor on its position, nor on the grid of the launch.
+ * cf_field: the same on host buffers, synchronous, on the current device. */
+#define CF_FIELD_MAX_NQ 4096
+#define CF_FIELD_MAX_NDIM 64
+#define CF_FIELD_MAX_ROWS 2147483647
+#define CF_FIELD_LAUNCH_ROWS 4194304 /* rows (workgroups) per grid: 2^31 threads at 512 per workgroup */
+#define CF_FIELD_NPAR 4
+#define CF_FIELD_NSCALAR 5
+enum cf_field_par { CF_FIELD_P_H0 = 0, CF_FIELD_P_OM = 1, CF_FIELD_P_W0 = 2, CF_FIELD_P_WA = 3 };
+enum cf_field_scalar {
+  CF_FIELD_PHI_TODAY = 0, CF_FIELD_T_TODAY = 1 /* Gyr */, CF_FIELD_HUBBLE_TIME = 2 /* Gyr */, CF_FIELD_PHI_MAX = 3,
+  CF_FIELD_T_MAX = 4 /* Gyr */
+};
+enum cf_field_status { CF_FIELD_OK = 0, CF_FIELD_PHANTOM = 1, CF_FIELD_BAD = 2 };
+typedef struct cf_field_desc {
+  int32_t struct_size; /* sizeof(cf_field_desc) as seen by the caller */
+  int32_t fde;         /* CF_FDE_WCDM | CF_FDE_THAWING | CF_FDE_CPL */
+  int32_t n_a;
+  int32_t ndim;        /* doubles per row of theta */
+  int32_t n_par;       /* 3: H0, Om, w0; 4: and wa (CF_FDE_CPL) */
+  int32_t _pad;
+  double a_min, a_max;
+  double orh2;         /* Omega_r h^2 (field.py:10: 4.1835e-05) */
+  cf_param par[CF_FIELD_NPAR];
+} cf_field_desc;
+typedef struct cf_field_queries {
+  const double* a_q;
+  const double* phi_q; /* NULL with n_phi >= 1: the rows' own grids */
+  const double* t_q;   /* NULL with n_t >= 1: the rows' own grids */
+  int32_t n_aq, n_phi, n_t, _pad;
+} cf_field_queries;
+typedef struct cf_field_out {
+  double *phi_a, *t_a, *w_a, *K_a, *V_a; /* [S, n_aq] */
+  double *phi_grid, *a_phi, *V_phi;      /* [S, n_phi] */
+  double *t_grid, *a_t, *phi_t;          /* [S, n_t] */
+  double* scalars;                       /* [S, CF_FIELD_NSCALAR] */
+  int32_t* status;                       /* [S] */
+} cf_field_out;
+
+/* How cf_field_device cuts S rows into grids: cf_field_launch_count(S) launches one after the other on the stream, launch k over
+ * the rows [begin, end) of cf_field_launch_range (at most CF_FIELD_LAUNCH_ROWS each; k out of range: the empty range [S, S)).
+ * Host arithmetic, no device needed. */
+int64_t cf_field_launch_count(int64_t S);
+void cf_field_launch_range(int64_t S, int64_t k, int64_t* begin, int64_t* end);
+int cf_field_device(const cf_field_desc* desc, const double* d_theta, int64_t S, const cf_field_queries* queries,
+                    const cf_field_out* out, void* hip_stream);
+int cf_field(const cf_field_desc* desc, const double* theta, int64_t S, const cf_field_queries* queries, const cf_field_out* out);
 
 #ifdef __cplusplus
 }
