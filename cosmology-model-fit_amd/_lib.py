@@ -173,6 +173,21 @@ class cf_field_out(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in FIELD_OUTPUTS + ("scalars", "status")]
 
 
+CF_RB_SN, CF_RB_BAO = 0, 1
+CF_RS_NCOL, CF_RESID_MAX_THR, CF_RESID_CHUNK = 10, 4, 4096
+RESID_BLOCKS = {"sn": CF_RB_SN, "bao": CF_RB_BAO}
+# cf_resid_col of include/cosmofit.h, in column order
+RESID_COLUMNS = ("mean", "std", "ss_res", "rmsd", "ss_tot", "r2", "skew", "kurtosis", "max_pull", "max_pull_index")
+# the ten chi2_blocks columns of cf_eval_parts / cf_resid_device
+CHI2_BLOCK_COLUMNS = ("chi2_sn", "chi2_bao", "chi2_cmb", "cmb_v0", "cmb_v1", "cmb_v2", "chi2_cc", "chi2_fs8", "z_star", "r_drag")
+
+
+class cf_resid_acc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n", C.c_int32), ("n_thr", C.c_int32), ("_pad", C.c_int32),
+                ("w_sum", C.c_void_p), ("mean", C.c_void_p), ("m2", C.c_void_p), ("exceed", C.c_void_p),
+                ("n_used", C.c_void_p), ("n_skipped", C.c_void_p)]
+
+
 class cf_info(C.Structure):
     _fields_ = [
         ("n_sn", C.c_int64), ("n_sn_pad", C.c_int64), ("packed_chol_bytes", C.c_int64),
@@ -256,6 +271,11 @@ EXPORTS = {
     "cf_field_launch_range": (None, [_I64, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
     "cf_field_device": (C.c_int, [C.POINTER(cf_field_desc), _VP, _I64, C.POINTER(cf_field_queries), C.POINTER(cf_field_out), _VP]),
     "cf_field": (C.c_int, [C.POINTER(cf_field_desc), _VP, _I64, C.POINTER(cf_field_queries), C.POINTER(cf_field_out)]),
+    "cf_resid_device": (C.c_int, [_VP, _VP, _I64, _VP, _I32, _VP, _I32, _VP, _VP, C.POINTER(cf_resid_acc), _VP]),
+    "cf_resid": (C.c_int, [_VP, _VP, _I64, _VP, _I32, _VP, _I32, _VP, _VP, C.POINTER(cf_resid_acc)]),
+    "cf_resid_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _VP, _I64, _I32, _VP, _I32, _VP, _VP, C.POINTER(cf_resid_acc)]),
+    "cf_resid_sigma": (C.c_int, [_VP, _I32, _VP]),
+    "cf_resid_set_chunk": (C.c_int, [_VP, _I64]),
 }
 
 

@@ -24,6 +24,7 @@
 #include "../../include/cosmofit.h"
 #include "cf_pack.h"
 #include "cosmofit_device.h"
+#include "cosmofit_resid.h"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
@@ -375,6 +376,12 @@ struct cf_handle {
   std::vector<cf_handle*> peers;
   std::vector<std::unique_ptr<cf_worker>> workers;
   std::mutex mu;
+  // fit report (cf_resid_device): sqrt(C_ii) of the SN / BAO data, computed on the host at cf_create and uploaded at the first
+  // call; per-chunk outputs of the accessor path (mu_corr, bao_theory, the chi^2 shares); rows per chunk (0: CF_RESID_CHUNK)
+  std::vector<double> sigma_sn_host, sigma_bao_host;
+  DevBuf sigma_sn, sigma_bao, r_mc, r_bt, r_blk, r_snb, r_fsb;
+  bool sigma_uploaded = false;
+  int64_t resid_rows = 0, resid_chunk = 0;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -651,6 +658,37 @@ struct DeviceScope {
   DeviceScope& operator=(const DeviceScope&) = delete;
 };
 
+// sqrt of the diagonal of inverse(inv_cov) (Gauss-Jordan with partial pivoting in extended precision): the errors of the BAO data
+// as the fit report plots them.  A singular matrix gives NaN.
+static void resid_bao_sigma(const double* inv_cov, int n, std::vector<double>& out) {
+  std::vector<long double> a((size_t)n * 2 * n, 0.0L);
+  const int ld = 2 * n;
+  for (int i = 0; i < n; ++i) {
+    for (int j = 0; j < n; ++j) a[(size_t)i * ld + j] = inv_cov[(size_t)i * n + j];
+    a[(size_t)i * ld + n + i] = 1.0L;
+  }
+  bool ok = true;
+  for (int k = 0; k < n && ok; ++k) {
+    int p = k;
+    for (int i = k + 1; i < n; ++i)
+      if (fabsl(a[(size_t)i * ld + k]) > fabsl(a[(size_t)p * ld + k])) p = i;
+    if (!(fabsl(a[(size_t)p * ld + k]) > 0.0L) || !std::isfinite((double)a[(size_t)p * ld + k])) { ok = false; break; }
+    if (p != k)
+      for (int j = 0; j < ld; ++j) std::swap(a[(size_t)p * ld + j], a[(size_t)k * ld + j]);
+    const long double inv = 1.0L / a[(size_t)k * ld + k];
+    for (int j = 0; j < ld; ++j) a[(size_t)k * ld + j] *= inv;
+    for (int i = 0; i < n; ++i) {
+      if (i == k) continue;
+      const long double f = a[(size_t)i * ld + k];
+      if (f != 0.0L)
+        for (int j = 0; j < ld; ++j) a[(size_t)i * ld + j] -= f * a[(size_t)k * ld + j];
+    }
+  }
+  out.assign((size_t)n, std::nan(""));
+  if (ok)
+    for (int i = 0; i < n; ++i) out[(size_t)i] = (double)sqrtl(a[(size_t)i * ld + n + i]);
+}
+
 static int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** out) {
   cf_handle* h = new cf_handle();
   auto bail = [&](int code) { cf_destroy(h); return code; };
@@ -794,6 +832,14 @@ static int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** 
       if (!(piv > 0.0) || !std::isfinite(piv))
         return bail(fail(CF_ERR_NOT_POSDEF, "cf_create: the Cholesky factor has a non-positive or non-finite pivot"));
     }
+    // sqrt(C_ii) = |row i of L| for the fit report (cf_resid_device): the factor is not kept on the host
+    h->sigma_sn_host.resize((size_t)c->n_sn);
+    for (int64_t i = 0; i < c->n_sn; ++i) {
+      long double acc = 0.0L;
+      const double* row = c->sn_chol + i * c->sn_chol_ld;
+      for (int64_t j = 0; j <= i; ++j) acc += (long double)row[j] * row[j];
+      h->sigma_sn_host[(size_t)i] = (double)sqrtl(acc);
+    }
     if (!prep.packed) {
       const double limit = c->probe_limit > 0.0 ? c->probe_limit : CF_PROBE_LIMIT;
       prep.solve_mode = c->solve_mode;
@@ -844,6 +890,7 @@ static int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** 
     d.bao_val = h->bao_val.as<const double>();
     d.bao_inv_cov = h->bao_inv_cov.as<const double>();
     d.bao_qty = h->bao_qty.as<const int32_t>();
+    resid_bao_sigma(c->bao_inv_cov, c->n_bao, h->sigma_bao_host);
   }
   if (d.n_aux > 0) {
     // interval of each BAO / growth-rate redshift on the grid, by the arithmetic of hermite_tab (cosmofit_kernels.hip); the
@@ -2270,6 +2317,202 @@ extern "C" int cf_curves(cf_handle* h, const double* theta, int64_t S, int32_t c
     if ((rc = cf_curves_launch(h->d, dth.as<const double>(), m, code, dz.as<const double>(), nz, dout.as<double>(), h->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(out + s0 * (int64_t)nz, dout.p, (size_t)m * nz * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  return CF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Fit report: residual statistics of every chain sample (kernels: cosmofit_resid.hip).  The residual rows come from the accessor
+// path of the likelihood (launch_path with a mu_corr buffer, as cf_eval_parts), one chunk of rows at a time into the handle's
+// workspace; the two kernels reduce each chunk behind it on the same stream.
+// ------------------------------------------------------------------------------------------------
+#define CF_RESID_MAX_ROWS (((int64_t)1 << 31) - 1)
+#define CF_RESID_MAX_CHUNK 65536
+
+extern "C" int cf_resid_check_args(int64_t n_sn, int32_t n_bao, int32_t is_quasar, int32_t n_devices, const void* theta, int64_t S,
+                                   int32_t block, const double* thresholds, int32_t n_thr, const void* sample, const void* chi2_blocks,
+                                   const cf_resid_acc* acc) {
+  const std::string F = "cf_resid: ";
+  if (is_quasar) return fail(CF_ERR_UNSUPPORTED, F + "a quasar handle has no accessor path to take the residuals from");
+  if (n_devices > 1) return fail(CF_ERR_UNSUPPORTED, F + "this handle spans several devices; use one handle per device");
+  if (block != CF_RB_SN && block != CF_RB_BAO) return fail(CF_ERR_INVALID, F + "block must be CF_RB_SN or CF_RB_BAO");
+  if (block == CF_RB_SN && n_sn <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no SN block");
+  if (block == CF_RB_BAO && n_bao <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no BAO block");
+  if (S < 0 || S > CF_RESID_MAX_ROWS) return fail(CF_ERR_INVALID, F + "S out of range");
+  if (n_thr < 0 || n_thr > CF_RESID_MAX_THR) return fail(CF_ERR_INVALID, F + "n_thr must be in 0..4");
+  if (n_thr > 0 && !thresholds) return fail(CF_ERR_INVALID, F + "null thresholds");
+  for (int k = 0; k < n_thr; ++k)
+    if (!std::isfinite(thresholds[k]) || thresholds[k] < 0.0) return fail(CF_ERR_INVALID, F + "thresholds must be finite and >= 0");
+  if (!sample && !chi2_blocks && !acc) return fail(CF_ERR_INVALID, F + "no output requested");
+  if (acc) {
+    const int64_t n = block == CF_RB_SN ? n_sn : n_bao;
+    if (acc->struct_size != (int32_t)sizeof(cf_resid_acc)) return fail(CF_ERR_INVALID, F + "cf_resid_acc.struct_size mismatch");
+    if (acc->n != n) return fail(CF_ERR_INVALID, F + "cf_resid_acc.n is not the number of data of the block");
+    if (acc->n_thr != n_thr) return fail(CF_ERR_INVALID, F + "cf_resid_acc.n_thr differs from n_thr");
+    if (!acc->w_sum || !acc->mean || !acc->m2 || !acc->n_used || !acc->n_skipped || (n_thr > 0 && !acc->exceed))
+      return fail(CF_ERR_INVALID, F + "null array in cf_resid_acc");
+  }
+  if (S > 0 && !theta) return fail(CF_ERR_INVALID, F + "null theta");
+  return CF_OK;
+}
+
+static int resid_check(cf_handle* h, const void* theta, int64_t S, int32_t block, const double* thresholds, int32_t n_thr,
+                       const void* sample, const void* chi2_blocks, const cf_resid_acc* acc) {
+  if (!h) return fail(CF_ERR_INVALID, "cf_resid: null handle");
+  return cf_resid_check_args(h->d.n_sn, h->d.n_bao, h->qsr ? 1 : 0, 1 + (int32_t)h->peers.size(), theta, S, block, thresholds, n_thr,
+                             sample, chi2_blocks, acc);
+}
+
+extern "C" int cf_resid_sigma(cf_handle* h, int32_t block, double* out) {
+  if (!h || !out) return fail(CF_ERR_INVALID, "cf_resid_sigma: null argument");
+  if (block != CF_RB_SN && block != CF_RB_BAO) return fail(CF_ERR_INVALID, "cf_resid_sigma: block must be CF_RB_SN or CF_RB_BAO");
+  const std::vector<double>& s = block == CF_RB_SN ? h->sigma_sn_host : h->sigma_bao_host;
+  if (h->qsr || s.empty()) return fail(CF_ERR_INVALID, "cf_resid_sigma: this likelihood has no such block");
+  memcpy(out, s.data(), s.size() * 8);
+  return CF_OK;
+}
+
+extern "C" int cf_resid_set_chunk(cf_handle* h, int64_t rows) {
+  if (!h) return fail(CF_ERR_INVALID, "cf_resid_set_chunk: null handle");
+  if (rows < 0 || rows > CF_RESID_MAX_CHUNK) return fail(CF_ERR_INVALID, "cf_resid_set_chunk: rows must be in 0..65536");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->resid_chunk = rows;
+  return CF_OK;
+}
+
+// Buffers for chunks of `rows` rows and the device copy of sigma.  Growing frees buffers an evaluation on a caller's stream may
+// still use: synchronise first, as ensure_workspace does.
+static int resid_prepare(cf_handle* h, int64_t rows) {
+  if (!h->sigma_uploaded) {
+    int rc;
+    if (!h->sigma_sn_host.empty() && (rc = upload_vec(h->sigma_sn, h->sigma_sn_host.data(), (int64_t)h->sigma_sn_host.size()))) return rc;
+    if (!h->sigma_bao_host.empty() && (rc = upload_vec(h->sigma_bao, h->sigma_bao_host.data(), (int64_t)h->sigma_bao_host.size())))
+      return rc;
+    h->sigma_uploaded = true;
+  }
+  if (rows <= h->resid_rows) return 0;
+  HIP_TRY(hipDeviceSynchronize());
+  const int64_t n = h->d.n_sn, nb = h->d.n_bao;
+  if (n > 0 && h->r_mc.ensure((size_t)rows * n * 8)) return CF_ERR_HIP;
+  if (nb > 0 && h->r_bt.ensure((size_t)rows * nb * 8)) return CF_ERR_HIP;
+  if (h->r_blk.ensure((size_t)rows * 8 * 8) || h->r_snb.ensure((size_t)rows * 8) || h->r_fsb.ensure((size_t)rows * 8)) return CF_ERR_HIP;
+  h->resid_rows = rows;
+  return 0;
+}
+
+// Arguments checked, h->mu held, the handle's device current.  Device pointers throughout.
+static int resid_run(cf_handle* h, const double* d_theta, int64_t S, const double* d_w, int32_t block, const double* thresholds,
+                     int32_t n_thr, double* d_sample, double* d_chi2_blocks, const cf_resid_acc* acc, hipStream_t st) {
+  int rc;
+  const int64_t chunk = std::min<int64_t>(S, h->resid_chunk > 0 ? h->resid_chunk : CF_RESID_CHUNK);
+  if ((rc = ensure_workspace(h, chunk))) return rc;
+  if ((rc = resid_prepare(h, chunk))) return rc;
+  const cf_dev_desc& d = h->d;
+  const bool want_blocks = d_chi2_blocks != nullptr;
+  cf_resid_src src{};
+  if (block == CF_RB_SN) {
+    src.rows = h->delta.as<const double>();
+    src.data = d.obs;
+    src.mu_corr = h->r_mc.as<const double>();
+    src.sigma = h->sigma_sn.as<const double>();
+    src.pitch = d.n_ld;
+    src.n = d.n_sn;
+    src.bao = 0;
+  } else {
+    src.rows = h->r_bt.as<const double>();
+    src.data = d.bao_val;
+    src.mu_corr = nullptr;
+    src.sigma = h->sigma_bao.as<const double>();
+    src.pitch = d.n_bao;
+    src.n = d.n_bao;
+    src.bao = 1;
+  }
+  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+    const int64_t m = std::min(chunk, S - s0);
+    if (want_blocks) {  // a block the likelihood lacks keeps 0, as in cf_eval_parts
+      HIP_TRY(hipMemsetAsync(h->r_snb.p, 0, (size_t)m * 8, st));
+      HIP_TRY(hipMemsetAsync(h->r_fsb.p, 0, (size_t)m * 8, st));
+      HIP_TRY(hipMemsetAsync(h->r_blk.p, 0, (size_t)m * 8 * 8, st));
+    }
+    // a mu_corr buffer selects the accessor form of the per-walker kernel (the reference's exact sequence, rows in row layout)
+    if ((rc = launch_path(h, d_theta + s0 * d.ndim, m, h->out.as<double>(), CF_OUT_CHI2, st, nullptr,
+                          d.n_sn > 0 ? h->r_mc.as<double>() : nullptr, want_blocks ? h->r_blk.as<double>() : nullptr,
+                          d.n_bao > 0 ? h->r_bt.as<double>() : nullptr, want_blocks ? h->r_snb.as<double>() : nullptr,
+                          want_blocks ? h->r_fsb.as<double>() : nullptr, nullptr)))
+      return rc;
+    cf_resid_blocks blk{h->r_snb.as<const double>(), h->r_blk.as<const double>(), h->r_fsb.as<const double>(),
+                        want_blocks ? d_chi2_blocks + 10 * s0 : nullptr};
+    if ((rc = cf_resid_launch(src, m, d_sample ? d_sample + (int64_t)CF_RS_NCOL * s0 : nullptr, blk, d_w ? d_w + s0 : nullptr, thresholds,
+                              n_thr, acc, st)))
+      return rc;
+  }
+  return CF_OK;
+}
+
+extern "C" int cf_resid_device(cf_handle* h, const double* d_theta, int64_t S, const double* d_w, int32_t block, const double* thresholds,
+                               int32_t n_thr, double* d_sample, double* d_chi2_blocks, cf_resid_acc* acc, void* hip_stream) {
+  int rc = resid_check(h, d_theta, S, block, thresholds, n_thr, d_sample, d_chi2_blocks, acc);
+  if (rc) return rc;
+  if (S == 0) return CF_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceScope on_device(h->device);
+  HIP_TRY(on_device.err);
+  return resid_run(h, d_theta, S, d_w, block, thresholds, n_thr, d_sample, d_chi2_blocks, acc, (hipStream_t)hip_stream);
+}
+
+// Host-buffer twin: rows in pieces through temporary device buffers on the handle's own stream; the accumulator goes to the
+// device once, is continued there piece by piece, and comes back at the end.
+#define CF_RESID_HOST_PIECE 65536
+
+extern "C" int cf_resid(cf_handle* h, const double* theta, int64_t S, const double* w, int32_t block, const double* thresholds,
+                        int32_t n_thr, double* sample, double* chi2_blocks, cf_resid_acc* acc) {
+  int rc = resid_check(h, theta, S, block, thresholds, n_thr, sample, chi2_blocks, acc);
+  if (rc) return rc;
+  if (S == 0) return CF_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceScope on_device(h->device);
+  HIP_TRY(on_device.err);
+  const int64_t piece = std::min<int64_t>(S, CF_RESID_HOST_PIECE);
+  const int ndim = h->d.ndim;
+  DevBuf dth, dw, ds, db, a_w, a_mean, a_m2, a_ex, a_used, a_skip;
+  if (dth.ensure((size_t)piece * ndim * 8)) return CF_ERR_HIP;
+  if (w && dw.ensure((size_t)piece * 8)) return CF_ERR_HIP;
+  if (sample && ds.ensure((size_t)piece * CF_RS_NCOL * 8)) return CF_ERR_HIP;
+  if (chi2_blocks && db.ensure((size_t)piece * 10 * 8)) return CF_ERR_HIP;
+  cf_resid_acc dacc{};
+  if (acc) {
+    const size_t nb = (size_t)acc->n * 8;
+    dacc = *acc;
+    if (a_w.ensure(nb) || a_mean.ensure(nb) || a_m2.ensure(nb) || a_used.ensure(nb) || a_skip.ensure(nb)) return CF_ERR_HIP;
+    if (n_thr > 0 && a_ex.ensure(nb * n_thr)) return CF_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(a_w.p, acc->w_sum, nb, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a_mean.p, acc->mean, nb, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a_m2.p, acc->m2, nb, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a_used.p, acc->n_used, nb, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a_skip.p, acc->n_skipped, nb, hipMemcpyHostToDevice, h->stream));
+    if (n_thr > 0) HIP_TRY(hipMemcpyAsync(a_ex.p, acc->exceed, nb * n_thr, hipMemcpyHostToDevice, h->stream));
+    dacc.w_sum = a_w.as<double>(); dacc.mean = a_mean.as<double>(); dacc.m2 = a_m2.as<double>(); dacc.exceed = a_ex.as<double>();
+    dacc.n_used = a_used.as<int64_t>(); dacc.n_skipped = a_skip.as<int64_t>();
+  }
+  for (int64_t s0 = 0; s0 < S; s0 += piece) {
+    const int64_t m = std::min(piece, S - s0);
+    HIP_TRY(hipMemcpyAsync(dth.p, theta + s0 * ndim, (size_t)m * ndim * 8, hipMemcpyHostToDevice, h->stream));
+    if (w) HIP_TRY(hipMemcpyAsync(dw.p, w + s0, (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
+    if ((rc = resid_run(h, dth.as<const double>(), m, w ? dw.as<const double>() : nullptr, block, thresholds, n_thr,
+                        sample ? ds.as<double>() : nullptr, chi2_blocks ? db.as<double>() : nullptr, acc ? &dacc : nullptr, h->stream)))
+      return rc;
+    if (sample) HIP_TRY(hipMemcpyAsync(sample + s0 * CF_RS_NCOL, ds.p, (size_t)m * CF_RS_NCOL * 8, hipMemcpyDeviceToHost, h->stream));
+    if (chi2_blocks) HIP_TRY(hipMemcpyAsync(chi2_blocks + s0 * 10, db.p, (size_t)m * 10 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  if (acc) {
+    const size_t nb = (size_t)acc->n * 8;
+    HIP_TRY(hipMemcpy(acc->w_sum, a_w.p, nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(acc->mean, a_mean.p, nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(acc->m2, a_m2.p, nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(acc->n_used, a_used.p, nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(acc->n_skipped, a_skip.p, nb, hipMemcpyDeviceToHost));
+    if (n_thr > 0) HIP_TRY(hipMemcpy(acc->exceed, a_ex.p, nb * n_thr, hipMemcpyDeviceToHost));
   }
   return CF_OK;
 }

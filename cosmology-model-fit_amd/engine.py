@@ -134,6 +134,7 @@ class LikelihoodEngine:
             p = params.get(name, _default_param(name))
             d.param[i].idx, d.param[i].scale, d.param[i].fixed = p.idx, p.scale, p.fixed
         keep = []
+        self.sn_z = self.bao_z = None  # redshifts of the SN / BAO data (the abscissae of a residual plot: fit_report)
         if sn is not None:
             z_cmb, z_hel, obs = _f64(sn["z_cmb"]), _f64(sn["z_hel"]), _f64(sn["obs"])
             chol = _f64(sn["chol"])
@@ -142,6 +143,7 @@ class LikelihoodEngine:
             step = None if sn.get("step") is None else _f64(sn["step"])
             keep += [z_cmb, z_hel, obs, chol, step]
             d.n_sn = z_cmb.size
+            self.sn_z = z_cmb.copy()
             d.sn_z_cmb, d.sn_z_hel, d.sn_obs, d.sn_step = _ptr(z_cmb), _ptr(z_hel), _ptr(obs), _ptr(step)
             d.sn_z_turn = float(sn.get("z_turn", 0.15))
             d.sn_vel_mode = 1 if sn.get("vel_mult", False) else 0
@@ -183,6 +185,7 @@ class LikelihoodEngine:
                 d.rd_fit[:] = [float(x) for x in bao["rd_fit"]]
                 d.rd_wm_mode = 1 if bao.get("rd_wm_late", False) else 0
             self.n_bao = int(bz.size)
+            self.bao_z = bz.copy()
         if cc is not None:
             cz, ch, cinv = _f64(cc["z"]), _f64(cc["h"]), _f64(cc["inv_cov"])
             if cz.size != ch.size or cinv.shape != (cz.size, cz.size):
@@ -321,6 +324,7 @@ class LikelihoodEngine:
                                  torch.cuda.current_stream(theta.device).cuda_stream)
             return out
 
+        f.engine = self  # what ShardedEnsemble.fit_report / DeviceNestedSampler.fit_report evaluate the residuals with
         return f
 
     def parts(self, theta):
@@ -409,6 +413,15 @@ class LikelihoodEngine:
         th = _f64(theta)
         out = D.Spec(self, names, **consts).host_columns(np.atleast_2d(th))
         return out[0] if th.ndim == 1 else out
+
+    def resid_sigma(self, block="sn"):
+        """sqrt(C_ii) of the block's data as the fit report uses it (cf_resid_sigma): the Cholesky factor's row norms for "sn",
+        the inverse of the inverse covariance for "bao"."""
+        if block not in L.RESID_BLOCKS:
+            raise ValueError(f"block must be one of {sorted(L.RESID_BLOCKS)}")
+        out = np.empty(self.n_sn if block == "sn" else self.n_bao)
+        L.check(L.lib().cf_resid_sigma(self._h, L.RESID_BLOCKS[block], _ptr(out)))
+        return out
 
     def enable_timing(self, slots=1, stride=1):
         """Keep HIP-event timings of the last `slots` timed evaluations (0 = off); only every `stride`-th evaluation is timed."""

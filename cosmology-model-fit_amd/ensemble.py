@@ -435,6 +435,18 @@ class ShardedEnsemble:
 
         return marginals.corner_data(self.get_chain(discard=discard, thin=thin, flat=True), **kw)
 
+    def fit_report(self, discard: int = 0, thin: int = 1, engine=None, **kw) -> dict:
+        """``fit_report.chain_report(engine, get_chain(discard, thin, flat=True), **kw)``: the residual block every script
+        ends with (sn/pantheon.py:150-201) for every stored sample, computed on the device.  engine: the likelihood's
+        ``LikelihoodEngine`` (default: the one behind ``engine.torch_log_prob()`` when that is the ensemble's callable).
+        Keywords: block, thresholds, center, n_data."""
+        from . import fit_report
+
+        if "weights" in kw:
+            raise TypeError("an ensemble's samples carry no weights")
+        eng = fit_report.engine_of(self.log_prob_fn, engine, "ShardedEnsemble.fit_report")
+        return fit_report.chain_report(eng, self.get_chain(discard=discard, thin=thin, flat=True), **kw)
+
     def mean_path(self, discard: int = 0) -> torch.Tensor:
         """The walker mean per stored step, [n, ndim] on the device: the black line of the reference's trace plot
         (corner_plot.py:30)."""

@@ -379,6 +379,19 @@ class DeviceNestedSampler:
         pts, w = self._posterior_on_device()
         return D.columns(spec, pts), w
 
+    def fit_report(self, engine=None, **kw) -> dict:
+        """``fit_report.chain_report`` of the posterior points with their weights exp(log_w): the residual block of the
+        nautilus scripts (bao/desi_fs_lya.py:96-141, sn/pantheon_dipole_xyz.py:118-143) for every posterior point.  engine:
+        the likelihood's ``LikelihoodEngine`` (default: the one behind ``engine.torch_log_prob()`` when that is the
+        sampler's callable).  Keywords: block, thresholds, center, n_data."""
+        from . import fit_report
+
+        if "weights" in kw:
+            raise TypeError("the nested sampler passes its own posterior weights")
+        eng = fit_report.engine_of(self.log_likelihood, engine, "DeviceNestedSampler.fit_report")
+        pts, w = self._posterior_on_device()
+        return fit_report.chain_report(eng, pts, weights=w, **kw)
+
     def mean_std(self):
         """``marginals.weighted_mean_std`` of the same points and weights: (mean [ndim], std [ndim]) on the device, what the
         nautilus scripts print per parameter (getdist's ``mean`` and ``std``)."""

@@ -19,6 +19,8 @@
  *   cf_eval_bao_at       bao_theory(z, qty, params) at ARBITRARY redshifts (post-fit plots)  bao/desi.py:38-56, bao/plot_predictions.py:24-45
  *   cf_eval_hz           H_z(z, params) at arbitrary redshifts (post-fit plots)             ohd/cc.py:95-96, ohd/plot_predictions.py:7-32
  *   cf_eval_fs8_at       fs8_theory(a, params) at arbitrary scale factors (post-fit plots) fs8/fs8.py:84-98,221-226
+ *   cf_resid_device      the residual block after the fit: R^2, RMSD, skewness, kurtosis of the residuals, their plot against
+ *                        sqrt(diag(cov)) -- for every row of a device chain    sn/pantheon.py:150-201, bao/desi_fs_lya.py:96-141
  *   cf_interp_hermite    interp_hermite                   interpolator.py:117-119
  *   cf_interp_pchip      interp_pchip                     interpolator.py:111-114
  *   cf_solve_triangular  solve_triangular (returns y.y)   solve_triangular.py:5-14
@@ -886,6 +888,82 @@ void cf_field_launch_range(int64_t S, int64_t k, int64_t* begin, int64_t* end);
 int cf_field_device(const cf_field_desc* desc, const double* d_theta, int64_t S, const cf_field_queries* queries,
                     const cf_field_out* out, void* hip_stream);
 int cf_field(const cf_field_desc* desc, const double* theta, int64_t S, const cf_field_queries* queries, const cf_field_out* out);
+
+/* ---- Fit report: residual statistics of every chain sample (csrc/cosmofit_resid.hip; the driver is
+ * cosmology-model-fit_amd/fit_report.py) ---------------------------------------------------------------------------------------
+ * The block every main() of the scripts ends with (sn/pantheon.py:150-201, bao/desi_fs_lya.py:96-141, sn/plotting.py:46-71),
+ * for every row of d_theta [S * ndim] instead of the one central theta.  The residual rows are those of the accessor path
+ * (cf_eval_parts: the reference's exact sequence, every SN variant), evaluated in chunks of at most CF_RESID_CHUNK rows into
+ * the handle's workspace and reduced there by two kernels; the likelihood is evaluated once per row.
+ *
+ * block = CF_RB_SN:  r_i = the row's residual vector, y_i = obs_i - mu_corr_i (`corrected_mags`), n = n_sn,
+ *                    sigma_i = sqrt(C_ii), C_ii = sum_{j <= i} L_ij^2 of the Cholesky factor given to cf_create
+ * block = CF_RB_BAO: r_i = val_i - bao_theory_i, y_i = val_i, n = n_bao, sigma_i = sqrt of the diagonal of inverse(bao_inv_cov)
+ * (sigma is computed on the host at cf_create and uploaded at the first call; cf_resid_sigma copies it out).
+ *
+ * d_sample [S * CF_RS_NCOL] (cf_resid_col), with m_k = (1 / n) sum_i (r_i - mean)^k:
+ *   mean, std = sqrt(m_2) (scipy.stats.norm.fit), ss_res = sum r^2, rmsd = sqrt(ss_res / n), ss_tot = sum (y - mean(y))^2,
+ *   r2 = 1 - ss_res / ss_tot, skew = m_3 / m_2^1.5, kurtosis = m_4 / m_2^2 - 3 (scipy.stats.skew / kurtosis: biased, Fisher),
+ *   max_pull = max_i |r_i| / sigma_i and its index i (np.argmax's rule: the first NaN, else the first maximum).
+ *   Two passes, every sum as lane-strided partials and a fixed butterfly: a row's bits depend neither on S, nor on its position,
+ *   nor on the chunking, nor on device / host pointers.  Plain IEEE: n = 1 or m_2 = 0 give NaN where numpy does; a non-finite
+ *   theta entry gives NaN in that row only.
+ * d_chi2_blocks [S * 10]: the chi2_blocks columns of cf_eval_parts.
+ * acc: running per-datum state over the rows, device arrays the caller owns and zeroes before the first call.  For datum i,
+ *   rows in order, a row is SKIPPED (n_skipped[i] += 1) when its weight is <= 0 or not finite or r_i is not finite; otherwise
+ *   (n_used[i] += 1), with w = d_w[s] (1 when d_w is NULL), West's update
+ *     W' = w_sum + w;  d = r_i - mean;  mean += (w d) / W';  m2 += (w d) (r_i - mean);  w_sum = W';
+ *     exceed[k * n + i] += w  if |r_i| > thresholds[k] * sigma_i
+ *   (Welford's for unit weights; variance = m2 / w_sum).  The accumulation is sequential in global row order: the same bits
+ *   for every chunk size and for every split of a chain into consecutive calls.
+ * d_w: NULL or [S].  thresholds: host array [n_thr], finite and >= 0, 0 <= n_thr <= CF_RESID_MAX_THR; only read with acc.
+ * Any of d_sample, d_chi2_blocks, acc may be NULL, not all three.
+ *
+ * Checks, all before the first HIP call (cf_resid_check_args states them without a handle): a quasar handle or a handle over
+ * several devices is CF_ERR_UNSUPPORTED; a block the handle lacks, S < 0 or > 2^31 - 1, n_thr out of range, a non-finite
+ * threshold, an acc whose struct_size / n / n_thr do not match or with a null array, no output at all, and (S > 0) a null
+ * d_theta are CF_ERR_INVALID.  S = 0 is a no-op.  The cosmic-chronometer and growth-rate blocks are not covered: the accessor
+ * path does not export their theory vectors.
+ *
+ * Stream contract: cf_resid_device evaluates into the handle's ONE workspace, so it obeys the contract of cf_eval_device
+ * (ordered with the handle's other evaluations, the first call after a stream switch blocks the host), NOT the independent,
+ * capturable one of cf_derived_device; the first call, and a call that has to grow the workspace, synchronise.
+ * cf_resid: the same on host buffers (acc's arrays host arrays too), synchronous, same bits. */
+#define CF_RB_SN 0
+#define CF_RB_BAO 1
+#define CF_RS_NCOL 10
+#define CF_RESID_MAX_THR 4
+#define CF_RESID_CHUNK 4096
+enum cf_resid_col {
+  CF_RS_MEAN = 0, CF_RS_STD = 1, CF_RS_SS_RES = 2, CF_RS_RMSD = 3, CF_RS_SS_TOT = 4, CF_RS_R2 = 5, CF_RS_SKEW = 6, CF_RS_KURT = 7,
+  CF_RS_MAX_PULL = 8, CF_RS_MAX_PULL_IDX = 9
+};
+typedef struct cf_resid_acc {
+  int32_t struct_size; /* sizeof(cf_resid_acc) as seen by the caller */
+  int32_t n;           /* data of the block */
+  int32_t n_thr;       /* rows of exceed */
+  int32_t _pad;
+  double* w_sum;       /* [n] weight of the used rows */
+  double* mean;        /* [n] */
+  double* m2;          /* [n] sum of w (r - mean)^2 */
+  double* exceed;      /* [n_thr * n] weight beyond each threshold (may be NULL when n_thr = 0) */
+  int64_t* n_used;     /* [n] */
+  int64_t* n_skipped;  /* [n] */
+} cf_resid_acc;
+
+int cf_resid_device(cf_handle* h, const double* d_theta, int64_t S, const double* d_w, int32_t block, const double* thresholds,
+                    int32_t n_thr, double* d_sample, double* d_chi2_blocks, cf_resid_acc* acc, void* hip_stream);
+int cf_resid(cf_handle* h, const double* theta, int64_t S, const double* w, int32_t block, const double* thresholds, int32_t n_thr,
+             double* sample, double* chi2_blocks, cf_resid_acc* acc);
+/* The argument rules above as host arithmetic on the facts of a handle (its n_sn, n_bao, whether it is a quasar handle, its
+ * number of devices): what cf_resid_device returns before it touches the device.  No handle and no device needed. */
+int cf_resid_check_args(int64_t n_sn, int32_t n_bao, int32_t is_quasar, int32_t n_devices, const void* theta, int64_t S, int32_t block,
+                        const double* thresholds, int32_t n_thr, const void* sample, const void* chi2_blocks, const cf_resid_acc* acc);
+/* sigma_i of a block into the host array out [n]; CF_ERR_INVALID for a block the handle lacks.  No HIP call. */
+int cf_resid_sigma(cf_handle* h, int32_t block, double* out);
+/* Rows per chunk of the following cf_resid_device / cf_resid calls of this handle, 1 .. 65536; 0 restores CF_RESID_CHUNK.
+ * The results do not depend on it: it exists so that tests can cross chunk boundaries with few rows. */
+int cf_resid_set_chunk(cf_handle* h, int64_t rows);
 
 #ifdef __cplusplus
 }
