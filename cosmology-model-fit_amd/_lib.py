@@ -188,6 +188,15 @@ class cf_resid_acc(C.Structure):
                 ("n_used", C.c_void_p), ("n_skipped", C.c_void_p)]
 
 
+CF_MOCK_CHUNK = 4096
+
+
+class cf_mock_set(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_mocks", C.c_int32), ("n_sn", C.c_int32), ("n_bao", C.c_int32),
+                ("n_cmb", C.c_int32), ("_pad", C.c_int32),
+                ("g_sn", C.c_void_p), ("g_bao", C.c_void_p), ("g_cmb", C.c_void_p), ("c", C.c_void_p)]
+
+
 class cf_info(C.Structure):
     _fields_ = [
         ("n_sn", C.c_int64), ("n_sn_pad", C.c_int64), ("packed_chol_bytes", C.c_int64),
@@ -276,6 +285,11 @@ EXPORTS = {
     "cf_resid_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _VP, _I64, _I32, _VP, _I32, _VP, _VP, C.POINTER(cf_resid_acc)]),
     "cf_resid_sigma": (C.c_int, [_VP, _I32, _VP]),
     "cf_resid_set_chunk": (C.c_int, [_VP, _I64]),
+    "cf_mock_eval_device": (C.c_int, [_VP, C.POINTER(cf_mock_set), _VP, _I64, _VP, _I32, _VP, _VP, _VP]),
+    "cf_mock_eval": (C.c_int, [_VP, C.POINTER(cf_mock_set), _VP, _I64, _VP, _I32, _VP, _VP]),
+    "cf_mock_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _I32, C.POINTER(cf_mock_set), _VP, _I64, _VP, _I32, _VP]),
+    "cf_mock_set_chunk": (C.c_int, [_VP, _I64]),
+    "cf_mock_normals": (C.c_int, [C.c_uint64, _I64, _I64, _I32, _VP, _VP]),
 }
 
 

@@ -24,6 +24,7 @@
 #include "../../include/cosmofit.h"
 #include "cf_pack.h"
 #include "cosmofit_device.h"
+#include "cosmofit_mock.h"
 #include "cosmofit_resid.h"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -382,6 +383,7 @@ struct cf_handle {
   DevBuf sigma_sn, sigma_bao, r_mc, r_bt, r_blk, r_snb, r_fsb;
   bool sigma_uploaded = false;
   int64_t resid_rows = 0, resid_chunk = 0;
+  int64_t mock_chunk = 0;  // rows per chunk of cf_mock_eval_device (0: CF_MOCK_CHUNK); it shares the fit report's chunk buffers
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -2513,6 +2515,140 @@ extern "C" int cf_resid(cf_handle* h, const double* theta, int64_t S, const doub
     HIP_TRY(hipMemcpy(acc->n_used, a_used.p, nb, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(acc->n_skipped, a_skip.p, nb, hipMemcpyDeviceToHost));
     if (n_thr > 0) HIP_TRY(hipMemcpy(acc->exceed, a_ex.p, nb * n_thr, hipMemcpyDeviceToHost));
+  }
+  return CF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Mock-data ensembles: the likelihood on per-row shifted data (kernels: cosmofit_mock.hip).  The residual rows come from the
+// accessor path, one chunk of rows at a time into the handle's workspace, exactly as resid_run gets them (the CMB theory vector
+// is columns 2..4 of r_blk); the likelihood's own value for out_kind lands in h->out and mock_shift_kernel adds the shift
+// behind it on the same stream.
+// ------------------------------------------------------------------------------------------------
+extern "C" int cf_mock_check_args(int64_t n_sn, int32_t n_bao, int32_t has_cmb, int32_t is_quasar, int32_t n_devices,
+                                  const cf_mock_set* set, const void* theta, int64_t S, const void* mock, int32_t out_kind,
+                                  const void* out) {
+  const std::string F = "cf_mock_eval: ";
+  if (is_quasar) return fail(CF_ERR_UNSUPPORTED, F + "a quasar handle has no accessor path to take the residuals from");
+  if (n_devices > 1) return fail(CF_ERR_UNSUPPORTED, F + "this handle spans several devices; use one handle per device");
+  if (!set) return fail(CF_ERR_INVALID, F + "null cf_mock_set");
+  if (set->struct_size != (int32_t)sizeof(cf_mock_set)) return fail(CF_ERR_INVALID, F + "cf_mock_set.struct_size mismatch");
+  if (set->n_mocks < 1) return fail(CF_ERR_INVALID, F + "n_mocks must be >= 1");
+  if (set->n_sn != 0 && n_sn <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no SN block");
+  if (set->n_bao != 0 && n_bao <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no BAO block");
+  if (set->n_cmb != 0 && !has_cmb) return fail(CF_ERR_INVALID, F + "this likelihood has no CMB block");
+  if (set->n_sn != 0 && (int64_t)set->n_sn != n_sn) return fail(CF_ERR_INVALID, F + "cf_mock_set.n_sn is neither 0 nor the handle's n_sn");
+  if (set->n_bao != 0 && set->n_bao != n_bao) return fail(CF_ERR_INVALID, F + "cf_mock_set.n_bao is neither 0 nor the handle's n_bao");
+  if (set->n_cmb != 0 && set->n_cmb != 3) return fail(CF_ERR_INVALID, F + "cf_mock_set.n_cmb must be 0 or 3");
+  if (set->n_sn == 0 && set->n_bao == 0 && set->n_cmb == 0) return fail(CF_ERR_INVALID, F + "no shifted block");
+  if ((set->n_sn != 0 && !set->g_sn) || (set->n_bao != 0 && !set->g_bao) || (set->n_cmb != 0 && !set->g_cmb) || !set->c)
+    return fail(CF_ERR_INVALID, F + "null array in cf_mock_set");
+  if (out_kind < CF_OUT_CHI2 || out_kind > CF_OUT_LOGP) return fail(CF_ERR_INVALID, F + "bad out_kind");
+  if (S < 0 || S > CF_RESID_MAX_ROWS) return fail(CF_ERR_INVALID, F + "S out of range");
+  if (S > 0 && (!theta || !mock || !out)) return fail(CF_ERR_INVALID, F + "null theta, mock or out");
+  return CF_OK;
+}
+
+static int mock_check(cf_handle* h, const cf_mock_set* set, const void* theta, int64_t S, const void* mock, int32_t out_kind,
+                      const void* out) {
+  if (!h) return fail(CF_ERR_INVALID, "cf_mock_eval: null handle");
+  return cf_mock_check_args(h->d.n_sn, h->d.n_bao, h->d.cmb_mode != 0 ? 1 : 0, h->qsr ? 1 : 0, 1 + (int32_t)h->peers.size(), set, theta,
+                            S, mock, out_kind, out);
+}
+
+extern "C" int cf_mock_set_chunk(cf_handle* h, int64_t rows) {
+  if (!h) return fail(CF_ERR_INVALID, "cf_mock_set_chunk: null handle");
+  if (rows < 0 || rows > CF_RESID_MAX_CHUNK) return fail(CF_ERR_INVALID, "cf_mock_set_chunk: rows must be in 0..65536");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->mock_chunk = rows;
+  return CF_OK;
+}
+
+// Arguments checked, h->mu held, the handle's device current.  Device pointers throughout (the set's arrays too).
+static int mock_run(cf_handle* h, const cf_mock_set& set, const double* d_theta, int64_t S, const int32_t* d_mock, int32_t out_kind,
+                    double* d_out, double* d_cross, hipStream_t st) {
+  int rc;
+  const int64_t chunk = std::min<int64_t>(S, h->mock_chunk > 0 ? h->mock_chunk : CF_MOCK_CHUNK);
+  if ((rc = ensure_workspace(h, chunk))) return rc;
+  if ((rc = resid_prepare(h, chunk))) return rc;
+  const cf_dev_desc& d = h->d;
+  cf_mock_args a{};
+  a.sn_rows = h->delta.as<const double>();
+  a.sn_pitch = d.n_ld;
+  a.bao_theory = h->r_bt.as<const double>();
+  a.bao_val = d.bao_val;
+  a.b8 = h->r_blk.as<const double>();
+  a.base = h->out.as<const double>();
+  a.g_sn = set.g_sn; a.g_bao = set.g_bao; a.g_cmb = set.g_cmb; a.c = set.c;
+  for (int i = 0; i < 3; ++i) a.cmb_prior[i] = d.cmb_prior[i];
+  a.n_sn = set.n_sn; a.n_bao = set.n_bao; a.n_cmb = set.n_cmb; a.n_mocks = set.n_mocks;
+  a.out_kind = out_kind;
+  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+    const int64_t m = std::min(chunk, S - s0);
+    // a mu_corr buffer selects the accessor form of the per-walker kernel (residual rows in row layout), as in resid_run
+    if ((rc = launch_path(h, d_theta + s0 * d.ndim, m, h->out.as<double>(), out_kind, st, nullptr,
+                          d.n_sn > 0 ? h->r_mc.as<double>() : nullptr, h->r_blk.as<double>(),
+                          d.n_bao > 0 ? h->r_bt.as<double>() : nullptr)))
+      return rc;
+    if ((rc = cf_mock_launch(a, m, d_mock + s0, d_out + s0, d_cross ? d_cross + 3 * s0 : nullptr, st))) return rc;
+  }
+  return CF_OK;
+}
+
+extern "C" int cf_mock_eval_device(cf_handle* h, const cf_mock_set* set, const double* d_theta, int64_t S, const int32_t* d_mock,
+                                   int32_t out_kind, double* d_out, double* d_cross, void* hip_stream) {
+  int rc = mock_check(h, set, d_theta, S, d_mock, out_kind, d_out);
+  if (rc) return rc;
+  if (S == 0) return CF_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceScope on_device(h->device);
+  HIP_TRY(on_device.err);
+  return mock_run(h, *set, d_theta, S, d_mock, out_kind, d_out, d_cross, (hipStream_t)hip_stream);
+}
+
+// Host-buffer twin: the set goes to the device once, the rows in pieces through temporary device buffers on the handle's stream.
+extern "C" int cf_mock_eval(cf_handle* h, const cf_mock_set* set, const double* theta, int64_t S, const int32_t* mock,
+                            int32_t out_kind, double* out, double* cross) {
+  int rc = mock_check(h, set, theta, S, mock, out_kind, out);
+  if (rc) return rc;
+  if (S == 0) return CF_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceScope on_device(h->device);
+  HIP_TRY(on_device.err);
+  const int64_t piece = std::min<int64_t>(S, CF_RESID_HOST_PIECE), K = set->n_mocks;
+  const int ndim = h->d.ndim;
+  DevBuf gs, gb, gc, cc, dth, dmk, dout, dcr;
+  cf_mock_set dset = *set;
+  if (set->n_sn) {
+    if (gs.ensure((size_t)K * set->n_sn * 8)) return CF_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(gs.p, set->g_sn, (size_t)K * set->n_sn * 8, hipMemcpyHostToDevice, h->stream));
+    dset.g_sn = gs.as<const double>();
+  }
+  if (set->n_bao) {
+    if (gb.ensure((size_t)K * set->n_bao * 8)) return CF_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(gb.p, set->g_bao, (size_t)K * set->n_bao * 8, hipMemcpyHostToDevice, h->stream));
+    dset.g_bao = gb.as<const double>();
+  }
+  if (set->n_cmb) {
+    if (gc.ensure((size_t)K * 3 * 8)) return CF_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(gc.p, set->g_cmb, (size_t)K * 3 * 8, hipMemcpyHostToDevice, h->stream));
+    dset.g_cmb = gc.as<const double>();
+  }
+  if (cc.ensure((size_t)K * 8)) return CF_ERR_HIP;
+  HIP_TRY(hipMemcpyAsync(cc.p, set->c, (size_t)K * 8, hipMemcpyHostToDevice, h->stream));
+  dset.c = cc.as<const double>();
+  if (dth.ensure((size_t)piece * ndim * 8) || dmk.ensure((size_t)piece * 4) || dout.ensure((size_t)piece * 8)) return CF_ERR_HIP;
+  if (cross && dcr.ensure((size_t)piece * 3 * 8)) return CF_ERR_HIP;
+  for (int64_t s0 = 0; s0 < S; s0 += piece) {
+    const int64_t m = std::min(piece, S - s0);
+    HIP_TRY(hipMemcpyAsync(dth.p, theta + s0 * ndim, (size_t)m * ndim * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(dmk.p, mock + s0, (size_t)m * 4, hipMemcpyHostToDevice, h->stream));
+    if ((rc = mock_run(h, dset, dth.as<const double>(), m, dmk.as<const int32_t>(), out_kind, dout.as<double>(),
+                       cross ? dcr.as<double>() : nullptr, h->stream)))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(out + s0, dout.p, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (cross) HIP_TRY(hipMemcpyAsync(cross + s0 * 3, dcr.p, (size_t)m * 3 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
   }
   return CF_OK;
 }

@@ -16,28 +16,13 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
+#include "cf_rng.h"
 
 #define CF_ENS_MAX_NDIM 16
 
 extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
-__device__ __forceinline__ uint64_t ens_mix(uint64_t x) {
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-// uniform in [0, 1): ensemble.py uniform01 with key = key0 + stream
-__device__ __forceinline__ double ens_uniform(uint64_t key0, int stream, int64_t id) {
-  uint64_t x = ens_mix((uint64_t)id * 0x9E3779B97F4A7C15ull + key0 + (uint64_t)stream);
-  x = ens_mix(x + 0x9E3779B97F4A7C15ull);
-  return (double)(x >> 11) * (1.0 / 9007199254740992.0);
-}
-// standard normal by Box-Muller from streams `stream`, `stream + 1`: ensemble.py normal01
-__device__ __forceinline__ double ens_normal(uint64_t key0, int stream, int64_t id) {
-  const double u1 = 1.0 - ens_uniform(key0, stream, id);
-  const double u2 = ens_uniform(key0, stream + 1, id);
-  return sqrt(-2.0 * log(u1)) * cos((2.0 * 3.14159265358979323846) * u2);
-}
+// ens_mix / ens_uniform / ens_normal: cf_rng.h (shared with cosmofit_mock.hip)
 
 // ---- the splits of a step (emcee's RedBlueMove: `nsplits` sets updated in turn, each proposing from the others) ----------
 // Walkers are taken in consecutive groups of S = n_splits (S = 2: pairs -- StretchMove, KDEMove; S = 3: triples -- emcee's

@@ -135,6 +135,10 @@ class LikelihoodEngine:
             d.param[i].idx, d.param[i].scale, d.param[i].fixed = p.idx, p.scale, p.fixed
         keep = []
         self.sn_z = self.bao_z = None  # redshifts of the SN / BAO data (the abscissae of a residual plot: fit_report)
+        # what mocks.MockSet needs of the data covariances: the SN factor the engine was built from (a reference, not a copy),
+        # the small inverse covariances, the CMB mode, and the blocks whose data it cannot shift
+        self.mock_data = dict(sn_chol=None, bao_val=None, bao_inv_cov=None, cmb_prior=None, cmb_inv_cov=None, cmb_mode=0,
+                              unshiftable=[])
         if sn is not None:
             z_cmb, z_hel, obs = _f64(sn["z_cmb"]), _f64(sn["z_hel"]), _f64(sn["obs"])
             chol = _f64(sn["chol"])
@@ -148,6 +152,7 @@ class LikelihoodEngine:
             d.sn_z_turn = float(sn.get("z_turn", 0.15))
             d.sn_vel_mode = 1 if sn.get("vel_mult", False) else 0
             d.sn_chol, d.sn_chol_ld = _ptr(chol), chol.shape[1]
+            self.mock_data["sn_chol"] = chol
             if sn.get("fixed_mu") is not None:
                 fm = _f64(sn["fixed_mu"])
                 if fm.size != z_cmb.size:
@@ -186,7 +191,9 @@ class LikelihoodEngine:
                 d.rd_wm_mode = 1 if bao.get("rd_wm_late", False) else 0
             self.n_bao = int(bz.size)
             self.bao_z = bz.copy()
+            self.mock_data["bao_val"], self.mock_data["bao_inv_cov"] = bv, binv
         if cc is not None:
+            self.mock_data["unshiftable"].append("cc")
             cz, ch, cinv = _f64(cc["z"]), _f64(cc["h"]), _f64(cc["inv_cov"])
             if cz.size != ch.size or cinv.shape != (cz.size, cz.size):
                 raise ValueError("cc: z, h must have n entries and inv_cov must be (n, n)")
@@ -195,6 +202,7 @@ class LikelihoodEngine:
             d.cc_f_mode = 1 if cc.get("f_inverse", False) else 0
         self.n_fs8 = 0
         if fs8 is not None:
+            self.mock_data["unshiftable"].append("fs8")
             fz, fv, finv, ffid = _f64(fs8["z"]), _f64(fs8["val"]), _f64(fs8["inv_cov"]), _f64(fs8["fid"])
             if not (fz.size == fv.size == ffid.size) or finv.shape != (fz.size, fz.size):
                 raise ValueError("fs8: z, val, fid must have n entries and inv_cov must be (n, n)")
@@ -212,6 +220,9 @@ class LikelihoodEngine:
             d.cmb_prior[:] = [float(x) for x in cmb["prior"]]
             d.cmb_inv_cov[:] = [float(x) for x in np.asarray(cmb["inv_cov"], dtype=np.float64).ravel()]
             d.zstar_fit[:] = [float(x) for x in tuple(cmb["zstar_fit"]) + ZSTAR_CONSTS]
+            self.mock_data["cmb_inv_cov"] = np.asarray(cmb["inv_cov"], dtype=np.float64).reshape(3, 3).copy()
+            self.mock_data["cmb_prior"] = np.asarray(cmb["prior"], dtype=np.float64).reshape(3).copy()
+            self.mock_data["cmb_mode"] = int(cmb["mode"])
         self.bounds = None if bounds is None else _f64(bounds).reshape(ndim, 2)
         d.bounds = _ptr(self.bounds)
         g = (L.cf_gauss_prior * max(len(gauss), 1))()
@@ -222,6 +233,8 @@ class LikelihoodEngine:
         for k, (idx, mean, sigma) in enumerate(chi2_gauss):
             cg[k].idx, cg[k].mean, cg[k].sigma = int(idx), float(mean), float(sigma)
         d.n_chi2_gauss, d.chi2_gauss = len(chi2_gauss), C.cast(cg, C.c_void_p)
+        if len(chi2_gauss):
+            self.mock_data["unshiftable"].append("chi2_gauss")
         d.cpl_wall = int(cpl_wall)
         self.ndim = ndim
         self.n_grid, self.z_max = int(n_grid), float(z_max)
@@ -257,6 +270,7 @@ class LikelihoodEngine:
                 self.n_bao = int(bz.size)
             self.n_qsr = int(qz.size)
             L.check(lib.cf_create_quasar(C.byref(d), C.byref(e), C.byref(self._h)))
+            self.mock_data["unshiftable"].append("quasar")
         del keep  # cf_create copied everything
 
     # ---- lifetime ---------------------------------------------------------------------------
@@ -264,6 +278,7 @@ class LikelihoodEngine:
         if getattr(self, "_h", None) is not None and self._h.value:
             L.lib().cf_destroy(self._h)
             self._h = C.c_void_p()
+        self.__dict__.pop("_mock_factor_dev", None)  # mocks.MockSet's device copy of the SN factor
 
     def __del__(self):
         try:

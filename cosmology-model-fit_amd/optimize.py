@@ -291,18 +291,19 @@ class _State:
         return s
 
 
-def _call(log_prob, theta):
+def _call(log_prob, theta, problem=None):
     import torch
 
-    out = log_prob(theta)
+    out = log_prob(theta) if problem is None else log_prob(theta, problem)
     if not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.device == theta.device and
             out.shape == (theta.shape[0],)):
         raise ValueError("log_prob must return a float64 tensor [W] on the device of theta")
     return out.contiguous()
 
 
-def _run(log_prob, p, u, theta, L, lib) -> OptimizeResult:
-    """Iterate from the start rows u / theta [B, ndim] (device) until every problem has a status."""
+def _run(log_prob, p, u, theta, L, lib, problem_index: bool = False) -> OptimizeResult:
+    """Iterate from the start rows u / theta [B, ndim] (device) until every problem has a status.  problem_index: the objective
+    is called as log_prob(theta, problem) with the int32 problem index of every row (see ``maximize``)."""
     import torch
 
     B, d, nf, K = u.shape[0], p.ndim, p.n_free, p.n_trials
@@ -310,7 +311,7 @@ def _run(log_prob, p, u, theta, L, lib) -> OptimizeResult:
     stream = torch.cuda.current_stream(dev).cuda_stream
     st = _State(B, d, dev)
     st.u.copy_(u)
-    f = _call(log_prob, theta)
+    f = _call(log_prob, theta, torch.arange(B, dtype=torch.int32, device=dev) if problem_index else None)
     fin = torch.isfinite(f)
     st.f.copy_(torch.where(fin, f, torch.full_like(f, -math.inf)))
     st.status.copy_(torch.where(fin, 0, NONFINITE_START).to(torch.int32))
@@ -324,9 +325,9 @@ def _run(log_prob, p, u, theta, L, lib) -> OptimizeResult:
     n_act, n_like, n_calls, iterations = int(act.numel()), B, 1, 0
     while n_act > 0:
         L.check(lib.cf_opt_stencil(pp, ps, act.data_ptr(), n_act, rows.data_ptr(), stream))
-        fs = _call(log_prob, rows[: n_act * 2 * nf])
+        fs = _call(log_prob, rows[: n_act * 2 * nf], act[:n_act].repeat_interleave(2 * nf) if problem_index else None)
         L.check(lib.cf_opt_direction(pp, ps, act.data_ptr(), n_act, fs.data_ptr(), trials.data_ptr(), stream))
-        ft = _call(log_prob, trials[: n_act * K])
+        ft = _call(log_prob, trials[: n_act * K], act[:n_act].repeat_interleave(K) if problem_index else None)
         L.check(lib.cf_opt_accept(pp, ps, act.data_ptr(), n_act, ft.data_ptr(), stream))
         L.check(lib.cf_opt_compact(act.data_ptr(), n_act, st.status.data_ptr(), nxt.data_ptr(), count.data_ptr(), stream))
         n_like += n_act * (2 * nf + K)
@@ -356,10 +357,15 @@ def _starts(p, x0: np.ndarray, key: Optional[int], L, lib):
 
 # ---- public interface ------------------------------------------------------------------------------------------------
 def maximize(log_prob: Callable, bounds, x0, *, free=None, h=1e-6, n_trials=4, gtol=1e-5, gtol_rel=None, max_iter=200,
-             c1=1e-4) -> OptimizeResult:
+             c1=1e-4, problem_index=False) -> OptimizeResult:
     """Maximise log_prob from the B start rows x0 [B, ndim] (tensor or array) inside the box bounds [ndim, 2].  free: the
     indices that move (default all); the others keep each row's value (the objective sees lo + u (hi - lo) with u clamped to
-    [2^-40, 1 - 2^-40], the same value within an ulp or two)."""
+    [2^-40, 1 - 2^-40], the same value within an ulp or two).
+
+    problem_index=True: every problem has an objective of its own (``mocks.MockSet``: a data set per problem).  The objective
+    is then called as ``log_prob(theta, problem)`` with ``problem`` an int32 device tensor [rows], the problem each row belongs
+    to: ``arange(B)`` for the start rows; for the stencil rows every entry of the active list repeated 2 n_free times (a
+    problem's rows are consecutive); for the trial rows every entry repeated n_trials times."""
     b = _bounds(bounds)
     ndim = b.shape[0]
     fr = _free_list(free, ndim)
@@ -368,7 +374,7 @@ def maximize(log_prob: Callable, bounds, x0, *, free=None, h=1e-6, n_trials=4, g
     L, lib = _require_gpu("maximize")
     p = _params(b, fr, o)
     u, th = _starts(p, x, None, L, lib)
-    return _run(log_prob, p, u, th, L, lib)
+    return _run(log_prob, p, u, th, L, lib, bool(problem_index))
 
 
 def _best_of(res: OptimizeResult, idx=None):
@@ -394,10 +400,11 @@ def _fixed(fixed, ndim: int, b: np.ndarray) -> dict:
     return out
 
 
-def best_fit(log_prob: Callable, bounds, *, n_starts=32, seed=0, x0=None, fixed=None, **options) -> FitResult:
+def best_fit(log_prob: Callable, bounds, *, n_starts=32, seed=0, x0=None, fixed=None, problem_index=False, **options) -> FitResult:
     """Multi-start maximization: the rows of x0 (e.g. the top log P rows of a device chain) first, then n_starts uniform
     random starts of ``seed``.  fixed = {index: value} holds those coordinates (the nested-model fit, e.g. {2: 0.0} for
-    v = 0).  Returns the best converged problem (ties: the lowest start index) and all problems."""
+    v = 0).  Returns the best converged problem (ties: the lowest start index) and all problems.  problem_index: as in
+    ``maximize`` (the problem is the start)."""
     b = _bounds(bounds)
     ndim = b.shape[0]
     fx = _fixed(fixed, ndim, b)
@@ -422,17 +429,19 @@ def best_fit(log_prob: Callable, bounds, *, n_starts=32, seed=0, x0=None, fixed=
     if n_starts:
         parts.append(_starts(p, rand, opt_key(seed, PURPOSE_BEST_FIT), L, lib))
     u, th = torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts])
-    res = _run(log_prob, p, u, th, L, lib)
+    res = _run(log_prob, p, u, th, L, lib, bool(problem_index))
     k, ok = _best_of(res)
     return FitResult(x=res.x[k].copy(), log_prob=float(res.log_prob[k]), status=int(res.status[k]), index=k, best_converged=ok,
                      problems=res)
 
 
-def profile(log_prob: Callable, bounds, index, grid, *, n_starts=8, seed=0, best: FitResult = None, **options) -> ProfileResult:
+def profile(log_prob: Callable, bounds, index, grid, *, n_starts=8, seed=0, best: FitResult = None, problem_index=False,
+            **options) -> ProfileResult:
     """Profile likelihood: at every grid point the profiled coordinates are held at the grid values and the rest maximised.
     1-D: index int, grid 1-D -> [G]; 2-D: index pair, grid pair (g1, g2) -> [G1, G2].  Start 0 of every grid point is the
     global best fit (``best``, computed with 32 starts of ``seed`` when not given) with the profiled coordinates overwritten;
-    starts 1 .. n_starts - 1 are random.  All G x n_starts problems run as one batch."""
+    starts 1 .. n_starts - 1 are random.  All G x n_starts problems run as one batch.  problem_index: as in ``maximize``
+    (problem p is start p % n_starts of grid point p // n_starts)."""
     b = _bounds(bounds)
     ndim = b.shape[0]
     if isinstance(index, (tuple, list)):
@@ -462,7 +471,7 @@ def profile(log_prob: Callable, bounds, index, grid, *, n_starts=8, seed=0, best
     import torch
 
     if best is None:
-        best = best_fit(log_prob, b, n_starts=32, seed=seed, **options)
+        best = best_fit(log_prob, b, n_starts=32, seed=seed, problem_index=problem_index, **options)
     shape = tuple(g_.size for g_ in grids)
     pts = np.stack([m.reshape(-1) for m in np.meshgrid(*grids, indexing="ij")], axis=1)  # [P, len(idx)]
     P = pts.shape[0]
@@ -473,7 +482,7 @@ def profile(log_prob: Callable, bounds, index, grid, *, n_starts=8, seed=0, best
     u, th = _starts(p, x0, opt_key(seed, PURPOSE_PROFILE), L, lib)
     u0, th0 = _starts(p, x0[::n_starts], None, L, lib)
     u[::n_starts], th[::n_starts] = u0, th0
-    res = _run(log_prob, p, u.contiguous(), th.contiguous(), L, lib)
+    res = _run(log_prob, p, u.contiguous(), th.contiguous(), L, lib, bool(problem_index))
     pick = np.array([_best_of(res, np.arange(q * n_starts, (q + 1) * n_starts))[0] for q in range(P)])
     values = res.log_prob[pick]
     fin = values[np.isfinite(values)]
