@@ -96,6 +96,8 @@ CF_QSR_BAO_NONE, CF_QSR_BAO_QUAD = 0, 1
 
 CF_MARG_MAX_NDIM, CF_MARG_MAX_BINS, CF_MARG_MAX_PAIRS, CF_MARG_MAX_SEGMENTS, CF_MARG_NOT_COUNTED = 16, 128, 256, 65536, 255
 
+CF_KDE_MAX_NDIM, CF_KDE_TILE, CF_KDE_SLICE, CF_KDE_QUERY_BLOCK, CF_KDE_SPLIT_BELOW_BLOCKS = 8, 256, 2048, 512, 512
+
 CF_OPT_MAX_NDIM, CF_OPT_MAX_TRIALS = 16, 8
 CF_OPT_RUNNING, CF_OPT_CONVERGED, CF_OPT_NOISE_FLOOR, CF_OPT_ITER_CAP, CF_OPT_NONFINITE_START, CF_OPT_NONFINITE_STENCIL = range(6)
 CF_OPT_NEED_RESET, CF_OPT_HAS_PAIR, CF_OPT_FRESH, CF_OPT_HAS_STEP = 1, 2, 4, 8
@@ -252,6 +254,7 @@ EXPORTS = {
     "cf_chain_acf_mean": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP]),
     "cf_marg_bin": (C.c_int, [_VP, _I64, _I32, _VP, _I32, _VP, _VP]),
     "cf_marg_hist": (C.c_int, [_VP, _VP, C.c_double, _I64, _I32, _I32, _VP, _I32, _VP, _VP, _I32, _VP]),
+    "cf_kde_sum_device": (C.c_int, [_VP, _VP, _I64, _I32, _VP, _I64, _I64, _VP, _VP, _VP]),
     "cf_ns_prior_draw": (C.c_int, [_VP, _I64, C.c_uint64, _VP, _VP, _VP]),
     "cf_ns_transform": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),
     "cf_ns_walk_start": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _I64, C.c_uint64, _VP, _VP, _VP, _VP]),

@@ -521,6 +521,28 @@ int cf_marg_bin(const double* d_x, int64_t n, int32_t ndim, const double* d_edge
 int cf_marg_hist(const uint8_t* d_idx, const double* d_w, double w_max, int64_t n, int32_t ndim, int32_t nbins,
                  const int32_t* pairs, int32_t npairs, int64_t* d_h1, int64_t* d_h2, int32_t n_segments, void* hip_stream);
 
+/* ---- kernel density sums (csrc/cosmofit_kde.hip; the driver is cosmology-model-fit_amd/tension.py) -----------------------
+ * All-pairs isotropic Gaussian kernel sums on already whitened points, everything float64 in device memory, row-major:
+ *   out[i] = sum over j != self(i) of  w_j exp(-0.5 |q_i - y_j|^2),     sq[i] = the sum of the squares of the same terms
+ * d_y [n * ndim] samples, d_w [n] weights (null: all 1), d_q [m * ndim] queries, d_out [m], d_sq [m] (null: not wanted).
+ * self_offset = -1: every sample counts.  self_offset >= 0: query i IS sample self_offset + i and that one term is left out
+ * inside the loop (exact leave-one-out; nothing is subtracted afterwards).
+ * Order of summation: slices of CF_KDE_SLICE consecutive samples, ascending j within a slice, then the slices ascending; so
+ * the bits of a row depend on the samples, the weights, the query and self(i) only (not on m, the row's position, the stream
+ * or repetition).  Samples are staged CF_KDE_TILE at a time.  A query further than ~37 units from every sample gives exactly
+ * 0.0 (exp underflows; no rescaling); a NaN or infinite query coordinate gives NaN in that row only.  Samples and weights
+ * must be finite (the caller checks).  CF_ERR_INVALID, before anything is launched, for: ndim outside 1 .. CF_KDE_MAX_NDIM,
+ * n < 1, m < 1, a null d_y / d_q / d_out, self_offset < -1, self_offset + m > n.  Device pointers only; the current device. */
+#define CF_KDE_MAX_NDIM 8
+#define CF_KDE_TILE 256
+#define CF_KDE_SLICE 2048
+/* launch geometry, stated for tests and tools (it never changes a bit of a result): a workgroup owns CF_KDE_QUERY_BLOCK
+ * queries; calls with fewer than CF_KDE_SPLIT_BELOW_BLOCKS query blocks give every slice a workgroup of its own */
+#define CF_KDE_QUERY_BLOCK 512
+#define CF_KDE_SPLIT_BELOW_BLOCKS 512
+int cf_kde_sum_device(const double* d_y, const double* d_w, int64_t n, int32_t ndim, const double* d_q, int64_t m,
+                      int64_t self_offset, double* d_out, double* d_sq, void* hip_stream);
+
 /* ---- nested sampling (csrc/cosmofit_nested.hip; the driver is cosmology-model-fit_amd/nested.py) -------------------------
  * Classic nested sampling with batch deletion on a device-resident live set: the per-step work of the constrained
  * differential-evolution walk that replaces the dead points.  Points live in the unit cube; theta = T(u) is the prior
