@@ -232,6 +232,7 @@ EXPORTS = {
     "cf_timed_calls": (C.c_int64, [_VP]),
     "cf_kernel_ms": (C.c_int, [_VP, _I64, C.POINTER(C.c_float * 2)]),
     "cf_kernel_ms3": (C.c_int, [_VP, _I64, C.POINTER(C.c_float * 3)]),
+    "cf_walker_form": (C.c_int, [_VP, _I64]),
     "cf_interp_hermite": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _I64, _VP]),
     "cf_interp_pchip": (C.c_int, [_VP, _I64, _VP, _VP, _I64, _VP]),
     "cf_solve_triangular": (C.c_int, [_VP, _I64, _I64, _VP, _I64, _VP]),

@@ -23,6 +23,7 @@
 
 #include "../../include/cosmofit.h"
 #include "cf_pack.h"
+#include "cf_stream_pack.h"
 #include "cosmofit_device.h"
 #include "cosmofit_mock.h"
 #include "cosmofit_resid.h"
@@ -56,6 +57,9 @@ __global__ void walker_kernel(cf_dev_desc d, const double* theta, int64_t W, dou
 template <int MODEL, int FDE>
 __global__ void walker_fast_kernel(cf_walker_args d, const double* theta, int64_t W, double* delta, d2* bao_nodes, double* theta_copy,
                                    int frag_b, int sn_parts);
+template <int MODEL, int FDE>
+__global__ void walker_stream_kernel(cf_walker_args d, cf_stream_args sa, const double* theta, int64_t W, double* delta, d2* bao_nodes,
+                                     double* theta_copy);
 template <int MODEL, int FDE, int LANES, int ROLES>
 __global__ void small_blocks_kernel(cf_dev_desc d, const double* theta, int64_t W, const d2* bao_nodes, double* chi2_extra,
                                     double* blocks_out, double* bao_out);
@@ -69,6 +73,7 @@ __global__ void hz_kernel(cf_dev_desc d, const double* theta, const double* z, i
 #define CF_DECLARE_WALKER(M, F)                                                                                            \
   extern template __global__ void walker_kernel<M, F>(cf_dev_desc, const double*, int64_t, double*, double*, double*, d2*, d2*); \
   extern template __global__ void walker_fast_kernel<M, F>(cf_walker_args, const double*, int64_t, double*, d2*, double*, int, int); \
+  extern template __global__ void walker_stream_kernel<M, F>(cf_walker_args, cf_stream_args, const double*, int64_t, double*, d2*, double*); \
   extern template __global__ void small_blocks_kernel<M, F, 16, 1>(cf_dev_desc, const double*, int64_t, const d2*, double*, \
                                                                    double*, double*);                                      \
   extern template __global__ void small_blocks_kernel<M, F, 64, 1>(cf_dev_desc, const double*, int64_t, const d2*, double*, \
@@ -92,6 +97,13 @@ static walker_fast_fn pick_walker_fast(int model, int fde) {
   static const walker_fast_fn table[2][4] = {
       {walker_fast_kernel<0, 0>, walker_fast_kernel<0, 1>, walker_fast_kernel<0, 2>, walker_fast_kernel<0, 3>},
       {walker_fast_kernel<1, 0>, walker_fast_kernel<1, 1>, walker_fast_kernel<1, 2>, walker_fast_kernel<1, 3>}};
+  return table[model][fde];
+}
+typedef void (*walker_stream_fn)(cf_walker_args, cf_stream_args, const double*, int64_t, double*, d2*, double*);
+static walker_stream_fn pick_walker_stream(int model, int fde) {
+  static const walker_stream_fn table[2][4] = {
+      {walker_stream_kernel<0, 0>, walker_stream_kernel<0, 1>, walker_stream_kernel<0, 2>, walker_stream_kernel<0, 3>},
+      {walker_stream_kernel<1, 0>, walker_stream_kernel<1, 1>, walker_stream_kernel<1, 2>, walker_stream_kernel<1, 3>}};
   return table[model][fde];
 }
 // The lean kernel arguments of the production per-walker kernel, and whether this descriptor may take it: register path of the
@@ -358,6 +370,8 @@ struct cf_handle {
   cf_dev_desc d{};
   PackedFactor pack;
   DevBuf z_cmb, z_hel, obs, sn_step, sn_rec, log10_tab;
+  DevBuf stream_rec, stream_row;  // the SN records in segment order and their rows (walker_stream_kernel: cf_stream_pack.h)
+  cf_stream_args sargs{};         // rec == null: the data do not fit the streaming form
   DevBuf bao_z, bao_val, bao_inv_cov, bao_qty, gl_x, gl_w, fixed_mu, cc_z, cc_h, cc_inv_cov, nu_grid, ln_grid, nu_sw, ln_sw, exp2_tab, sn_lin, sn_dir;
   DevBuf theta, out, delta, ypk, chi2_extra, nonfinite;
   DevBuf fs8_z, fs8_val, fs8_inv_cov, fs8_fid, fs8_step_of, fs8_order, fs8_tab, fs8_pts;
@@ -825,6 +839,28 @@ static int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** 
       if (hipMemcpy(h->sn_rec.p, rec.data(), rec.size() * sizeof(cf_d4), hipMemcpyHostToDevice) != hipSuccess)
         return bail(fail(CF_ERR_HIP, "hipMemcpy(sn_rec) failed"));
       d.sn_rec = h->sn_rec.as<const cf_d4>();
+      // the same records in the order the streaming form evaluates them (by grid segment of z_cmb), with their rows
+      cf_stream_plan plan;
+      if (d.chunk_shift == 3 &&
+          cf_stream_assign(c->sn_z_cmb, (d.has_vstep && !d.lin_in_rec) ? step.data() : nullptr, c->n_sn, d.n_grid, d.inv_step, d.z_max, plan)) {
+        std::vector<cf_d4> srec((size_t)c->n_sn + CF_STREAM_REC_SLACK, cf_d4{1.0, 1.0, 1.0, 0.0});
+        std::vector<int32_t> srow((size_t)c->n_sn + CF_STREAM_REC_SLACK, 0);
+        for (int64_t j = 0; j < c->n_sn; ++j) {
+          srow[(size_t)j] = plan.row[(size_t)j];
+          srec[(size_t)j] = rec[(size_t)plan.row[(size_t)j]];
+        }
+        int rcs;
+        if ((rcs = upload_vec(h->stream_rec, reinterpret_cast<const double*>(srec.data()), (int64_t)srec.size() * 4))) return bail(rcs);
+        if (h->stream_row.ensure(srow.size() * sizeof(int32_t))) return bail(CF_ERR_HIP);
+        if (hipMemcpy(h->stream_row.p, srow.data(), srow.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
+          return bail(fail(CF_ERR_HIP, "hipMemcpy(stream_row) failed"));
+        h->sargs.rec = h->stream_rec.as<const cf_d4>();
+        h->sargs.row = h->stream_row.as<const int32_t>();
+        for (int s = 0; s <= CF_STREAM_MAX_SEGS; ++s) h->sargs.seg_off[s] = plan.seg_off[s];
+        h->sargs.n_seg = plan.n_seg;
+        h->sargs.max_step = plan.max_step;
+        h->sargs.zp1_max = plan.zp1_max;
+      }
       int rc2;
       if ((rc2 = upload_log10_table(h->log10_tab))) return bail(rc2);
       d.log10_tab = h->log10_tab.p;
@@ -1157,6 +1193,18 @@ extern "C" int cf_get_info(cf_handle* h, cf_info* info) {
   return CF_OK;
 }
 
+// Which form of the per-walker kernel cf_eval / cf_eval_device run for a batch of W walkers: 0 the workgroup form
+// (walker_fast_kernel), 1 the streaming form (walker_stream_kernel), 2 the generic kernel (or a likelihood with a kernel of its own).
+static bool small_frag_b(const cf_handle* h, int64_t Wc);
+static int sn_parts_for(const cf_dev_desc& d, int64_t Wc);
+static bool walker_stream_chosen(const cf_handle* h, int64_t Wc, bool frag_b, int sn_parts);
+extern "C" int cf_walker_form(cf_handle* h, int64_t W) {
+  if (!h || W < 1) return fail(CF_ERR_INVALID, "cf_walker_form: null handle or W < 1");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->qsr || !walker_fast_ok(h->d)) return 2;
+  return walker_stream_chosen(h, W, small_frag_b(h, W), sn_parts_for(h->d, W)) ? 1 : 0;
+}
+
 extern "C" int cf_enable_timing(cf_handle* h, int slots) {
   if (!h) return fail(CF_ERR_INVALID, "cf_enable_timing: null handle");
   if (slots < 0 || slots > 4096) return fail(CF_ERR_INVALID, "cf_enable_timing: slots must be in 0..4096");
@@ -1355,6 +1403,55 @@ static int launch_tri_gemm(const TriGemmArgs& a, hipStream_t st) {
   return tri_gemm_panel_width(a.W) == 32 ? launch_tri_gemm_t<2, 2>(a, st) : launch_tri_gemm_t<1, 2>(a, st);
 }
 
+// a small batch of the production path takes the fragment-ordered residuals (launch_eval)?
+static bool small_frag_b(const cf_handle* h, int64_t Wc) {
+  static const bool frag_env = cf_tune("small_frag", 1) != 0;
+  const cf_dev_desc& d = h->d;
+  const bool small_solve = d.n_sn > 0 && h->solve_mode == CF_SOLVE_INVERSE_GEMM && h->partial4.p && Wc <= small_batch_max();
+  return frag_env && small_solve && walker_fast_ok(d) && !h->qsr;
+}
+// workgroups per walker of walker_fast_kernel (CF_TUNE sn_parts=1|2|4 overrides)
+static int sn_parts_for(const cf_dev_desc& d, int64_t Wc) {
+  static const int parts_env = (int)cf_tune("sn_parts", 0);
+  int sn_parts = parts_env > 0 ? parts_env : (Wc <= 64 ? 4 : (Wc <= 160 ? 2 : 1));  // measured: W = 16 26.5 -> 25.3 us, W = 64 31.5 -> 30.1 us per call
+  if (sn_parts > CF_SN_PARTS_MAX || d.n_sn == 0) sn_parts = 1;
+  return sn_parts;
+}
+// The streaming form of the production per-walker kernel (walker_stream_kernel): may this likelihood take it, and does a batch of
+// Wc walkers?  Same bits as walker_fast_kernel, so the switch is a matter of speed alone.  CF_TUNE walker_stream=0 never,
+// =1 whenever allowed, unset: by the batch size (walker_stream_chosen), for the families whose instantiation keeps its register budget.
+// The instantiations that spill vector registers at the 128 the form allows (four waves per SIMD) lose: physical-density CPL
+// 0.2844 -> 0.2956 ms per step at 4096 walkers (profiles/walker_stream_sweep_raw.txt).  From the compiler's resource report: flat CPL,
+// physical wCDM and physical CPL.  They run the streaming form only when CF_TUNE asks for it.
+static bool walker_stream_in_budget(int ez_model, int fde) {
+  return !(fde == CF_FDE_CPL_D || (ez_model == CF_EZ_PHYSICAL_D && fde == CF_FDE_WCDM_D));
+}
+static bool walker_stream_ok(const cf_handle* h) {
+  const cf_dev_desc& d = h->d;
+  return walker_fast_ok(d) && !h->qsr && d.n_sn > 0 && h->sargs.rec != nullptr && d.n_grid <= CF_STREAM_SEG * CF_STREAM_MAX_SEGS;
+}
+// One ROUND is the walkers the chip holds at once in the streaming form: 16 one-wave walkers per CU (LDS: four workgroups of four
+// windows), 4096 on 256 CUs.  Waves start together and run in phase, so a short last round runs on a nearly empty chip.  Measured,
+// ms per step of the flat-LCDM benchmark, workgroup form (parent library) -> every walker streaming, interleaved:
+//   512 walkers 0.0443 -> 0.0603, 1024: 0.0731 -> 0.0840, 2048: 0.1258 -> 0.1303, 8192: 0.4359 -> 0.4259
+//                                       (this library with CF_TUNE walker_stream=0 / 1: profiles/walker_stream_sweep_raw.txt)
+//   4096: 0.22350 -> 0.22046 (6 pairs, sd 0.0003)                                         (profiles/walker_stream_ab_default_raw.txt)
+//   4100: 0.2403 -> 0.2438, 4608: 0.2534 -> 0.2550, 5120: 0.2789 -> 0.2772, 6144: 0.3314 -> 0.3274, 7168: 0.3874 -> 0.3819,
+//   8200: 0.4548 -> 0.4513, 8704: 0.4907 -> 0.4814, 9000: 0.5015 -> 0.4914, 12000: 0.6442 -> 0.6343
+//                                                                                         (profiles/walker_stream_tail_sweep_raw.txt)
+// So: below one round never; one round and a last round that is empty or at least a quarter full; two rounds or more always.
+// (Streaming the full rounds and giving the rest to the workgroup form in a second launch was measured too, same file: the launch
+// costs what one round gains -- 4100: 0.2416, 6144: 0.3325 -- and it was dropped.)
+static bool walker_stream_chosen(const cf_handle* h, int64_t Wc, bool frag_b, int sn_parts) {
+  static const int mode = (int)cf_tune("walker_stream", -1);
+  if (mode == 0 || frag_b || sn_parts > 1 || !walker_stream_ok(h)) return false;
+  if (mode > 0) return true;
+  if (!walker_stream_in_budget(h->d.ez_model, h->d.fde)) return false;
+  const int64_t round = (int64_t)(4 * CF_STREAM_WAVES) * (h->cu_count > 0 ? h->cu_count : 256);
+  const int64_t full = Wc / round, rest = Wc % round;
+  return full >= 2 || (full == 1 && (rest == 0 || 4 * rest >= round));
+}
+
 // One evaluation of W walkers on stream `st`: per-walker kernel (distance table, residuals; the small-blocks / growth kernels of a
 // joint likelihood), then the solve + chi^2 + epilogue (or the bare epilogue for likelihoods without an SN block).
 // ev: 4 timing events or null.
@@ -1371,9 +1468,7 @@ static int launch_eval(cf_handle* h, const double* th, int64_t Wc, double* out, 
   double* extra = (h->has_small_blocks || h->has_growth || h->qsr) ? h->chi2_extra.as<double>() : nullptr;
   // a small batch of the production path: walker_fast_kernel writes the residuals in the fragment order the small-batch solve
   // kernel loads them in (one contiguous 1 KiB load per K-step pair instead of a 16-row gather: sn_fast_loop, FRAG)
-  static const bool frag_env = cf_tune("small_frag", 1) != 0;
-  const bool small_solve = d.n_sn > 0 && h->solve_mode == CF_SOLVE_INVERSE_GEMM && h->partial4.p && Wc <= small_batch_max();
-  const bool frag_b = frag_env && small_solve && !dm_out && !mucorr_out && walker_fast_ok(d) && !h->qsr;
+  const bool frag_b = !dm_out && !mucorr_out && small_frag_b(h, Wc);
   if (h->qsr) {  // quasar likelihood: its own per-walker kernel writes the SN residuals (row layout) and the quasar / BAO chi^2
     double* th_copy = h->theta_on_host ? h->theta.as<double>() : nullptr;
     int rc = cf_qsr_launch(h->qsr, th, Wc, delta, extra, out_kind, th_copy, st);
@@ -1390,11 +1485,13 @@ static int launch_eval(cf_handle* h, const double* th, int64_t Wc, double* out, 
       double* th_copy = h->theta_on_host ? h->theta.as<double>() : nullptr;
       // a small batch leaves most of the chip idle: several workgroups per walker, each with the walker's table and a share of
       // its SNe (CF_TUNE sn_parts=1|2|4 overrides)
-      static const int parts_env = (int)cf_tune("sn_parts", 0);
-      int sn_parts = parts_env > 0 ? parts_env : (Wc <= 64 ? 4 : (Wc <= 160 ? 2 : 1));  // measured: W = 16 26.5 -> 25.3 us, W = 64 31.5 -> 30.1 us per call
-      if (sn_parts > CF_SN_PARTS_MAX || d.n_sn == 0) sn_parts = 1;
-      hipLaunchKernelGGL(pick_walker_fast(d.ez_model, d.fde), dim3((unsigned)(Wc * sn_parts)), dim3(512), lds, st, walker_args_of(d), th,
-                         Wc, delta, bao_nodes, th_copy, frag_b ? 1 : 0, sn_parts);
+      const int sn_parts = sn_parts_for(d, Wc);
+      if (walker_stream_chosen(h, Wc, frag_b, sn_parts))  // a large batch: one wave per walker, the table streamed in segments
+        hipLaunchKernelGGL(pick_walker_stream(d.ez_model, d.fde), dim3((unsigned)((Wc + CF_STREAM_WAVES - 1) / CF_STREAM_WAVES)),
+                           dim3(64 * CF_STREAM_WAVES), 0, st, walker_args_of(d), h->sargs, th, Wc, delta, bao_nodes, th_copy);
+      else
+        hipLaunchKernelGGL(pick_walker_fast(d.ez_model, d.fde), dim3((unsigned)(Wc * sn_parts)), dim3(512), lds, st, walker_args_of(d), th,
+                           Wc, delta, bao_nodes, th_copy, frag_b ? 1 : 0, sn_parts);
       if (th_copy) th = th_copy;
     } else
       hipLaunchKernelGGL(pick_walker(d.ez_model, d.fde), dim3((unsigned)Wc), dim3(512), lds, st, d, th, Wc, delta, dm_out, mucorr_out,

@@ -156,6 +156,53 @@ struct cf_walker_args {
   const int32_t* bao_base;
 };
 
+// The STREAMING form of the production per-walker kernel (walker_stream_kernel: one wave per walker, the grid in segments of
+// CF_STREAM_SEG nodes) takes these beside cf_walker_args.  A segment's LDS window holds its own nodes and, in front of them, the
+// last CF_STREAM_HALO nodes of the segment before.  The SNe are packed at cf_create in segment order (cf_stream_pack.h): segment
+// s evaluates records seg_off[s] .. seg_off[s + 1] - 1 and stores each result to its original row.
+#define CF_STREAM_SEG 512
+#define CF_STREAM_HALO 64
+#define CF_STREAM_WAVES 4          // walkers (waves) per workgroup: they share the two small reduction tables
+#define CF_STREAM_MAX_SEGS 8       // grids of at most 4096 nodes
+#define CF_STREAM_REC_SLACK 128    // spare records behind the last one: the loop's look-ahead needs no bounds check
+// a walker whose SNe move at most this many nodes (as bounded by cf_stream_shift_bound) away from their z_cmb keeps every
+// interval it reads inside the window it was packed for: the packing leaves HALO / 2 nodes to either edge, the bound is on the
+// real-valued shift, truncation to a node index costs one node on either end and the interval reads one node above (HALO / 2 - 4 + 3)
+#define CF_STREAM_GUARD_NODES (CF_STREAM_HALO / 2 - 4)
+struct cf_stream_args {
+  const cf_d4* rec;    // [n_sn + CF_STREAM_REC_SLACK] the records of sn_rec in segment order
+  const int32_t* row;  // [n_sn + CF_STREAM_REC_SLACK] original row of each
+  int32_t seg_off[CF_STREAM_MAX_SEGS + 1];
+  int32_t n_seg;
+  double max_step;  // max |step weight| (0 without a velocity step: z_cosmo = z_cmb then)
+  double zp1_max;   // 1 + max z_cmb
+};
+
+// Node of the interval hermite_fast reads at redshift z (nodes i and i + 1), and the segment whose window holds it at least
+// CF_STREAM_HALO / 2 nodes from either edge: the host packs by it (z = z_cmb), the kernel's slow path evaluates by it (z = z_cosmo).
+#ifdef __HIPCC__
+#define CF_HD_INLINE __host__ __device__ static inline
+#else
+#define CF_HD_INLINE static inline
+#endif
+CF_HD_INLINE int cf_stream_node(double z, int G, double inv_step, double z_max) {
+  if (z <= 0.0) return 0;
+  if (!(z < z_max)) return G - 2;  // the extrapolation above the grid, and NaN, read node G - 1 (hermite_fast)
+  const int i = (int)(z * inv_step);
+  return i > G - 2 ? G - 2 : i;
+}
+CF_HD_INLINE int cf_stream_segment(int node, int n_seg) {
+  const int s = (node + CF_STREAM_HALO / 2) / CF_STREAM_SEG;
+  return s > n_seg - 1 ? n_seg - 1 : s;
+}
+// Upper bound, in grid nodes, of |z_cosmo - z_cmb| over the SNe for a peculiar velocity v100 [km/s]: z_cosmo = (1 + z_cmb) / (1 + z_pec) - 1
+// with |z_pec| <= a = |v100| max|step| / c moves by at most (1 + z_cmb) a / (1 - a).  NaN for NaN input; meaningless for a >= 1.
+CF_HD_INLINE double cf_stream_shift_bound(double v100, double max_step, double zp1_max, double c, double inv_step, double* a_out) {
+  const double a = (v100 < 0.0 ? -v100 : v100) * max_step / c;
+  *a_out = a;
+  return zp1_max * (a / (1.0 - a)) * inv_step;
+}
+
 // What the prior / output epilogue (finalize_value: sn/pantheon.py:80-97) reads, and nothing else: 0.7 KB.  The solve kernels take
 // a POINTER to the handle's device copy (cf_handle::epi): with the 1.9 KB cf_dev_desc by value they carried 44-46 SGPR spills,
 // because the epilogue of the one last-arriving workgroup kept the whole descriptor live in scalar registers in all of them.

@@ -6,7 +6,9 @@
 //        cumulative trapezoid as chunk-sequential sums + a wave64 DPP scan + LDS carry, the table {cum_dm, dh} staged
 //        in LDS (G * 16 B = 64 KB), cubic Hermite at z_cosmo(theta) of the N supernovae, residual -> Delta[w][0..n_ld).
 //        walker_fast_kernel is the production form (lean kernel arguments, theta row across the lanes); walker_kernel
-//        keeps the accessor / calibrator / direction-dependent / long-grid paths.
+//        keeps the accessor / calibrator / direction-dependent / long-grid paths.  For large batches (4096 walkers, from 5120) walker_stream_kernel
+//        replaces it: one WAVE per walker, the table built and consumed 512 nodes at a time in a 9.6 KB LDS window, the SNe
+//        packed by grid segment at cf_create; the same bits.
 //
 //   tri_gemm_chi2_kernel / tri_gemm_small_kernel   (a11)   chi^2 = || X Delta ||^2 with X = L^-1 inverted once on the
 //        host: a triangular GEMM on FP64 matrix cores (v_mfma_f64_16x16x4_f64) with no dependency between 64-row
@@ -925,6 +927,212 @@ walker_fast_kernel(cf_walker_args d, const double* __restrict__ theta, int64_t W
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The STREAMING production form for large batches: ONE WAVE per walker, no workgroup barrier.  The wave walks the grid in
+// segments of CF_STREAM_SEG = 512 nodes and does for segment s exactly what wave s of walker_fast_kernel's workgroup does (the
+// same chunk_eval, scan and carry expression, so the same bits); it keeps {cum, dh} of the segment, and the last CF_STREAM_HALO
+// nodes of the segment before, in a wave-private LDS window of 9.6 KB instead of the whole 72 KB table, and evaluates after
+// each segment the SNe packed for it at cf_create (cf_stream_pack.h).  The walker-uniform prologue runs once instead of in
+// each of eight waves; four walkers share a workgroup only for the two small reduction tables.
+//
+// Window: node q of [halo | segment] (q = g - 512 s + 64) sits at entry q + q / 16, and the spare entry behind every 16 nodes
+// holds a copy of the node after it, so that hermite_fast's two reads stay adjacent (DistTable with chs = 4).  A lane's eight
+// 16-byte stores then start 8.5 entries = 34 banks apart from its neighbour's: conflict-free over 16 lanes.
+// ------------------------------------------------------------------------------------------------
+#define CF_STREAM_WIN ((CF_STREAM_HALO + CF_STREAM_SEG) / 16 * 17)  // entries per window
+#define CF_STREAM_Q0 (CF_STREAM_HALO + CF_STREAM_HALO / 16)         // entry of the segment's first node
+
+__device__ __forceinline__ double uniform_f64(double v) {  // a wave-uniform value, moved to a scalar register pair
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+// a wave's LDS stores, then loads by other lanes of the same wave: the LDS executes a wave's accesses in order; this keeps the
+// compiler from reordering them
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The SNe of one segment: the arithmetic of sn_fast_loop's one_sn on the window.  FAST: the walker passed the guard, its SNe
+// are where they were packed (records lo .. hi - 1 = the segment's); otherwise every SN of the walker is looked at and those
+// whose interval at z_cosmo(theta) belongs to this segment are evaluated.
+template <bool PM1, bool LIN, bool FAST, class D>
+__device__ __forceinline__ void sn_stream_segment(const D& d, const cf_stream_args& sa, const DistTable& T, const d2* __restrict__ log_tab,
+                                                  double* __restrict__ out, double off, double v100, double lin, double r_pos,
+                                                  double r_neg, double c0, int s, unsigned j, unsigned end, d4 ra, int rowa) {
+  auto one_sn = [&](const d4& r, int row) {
+    const double za = r[0], st = r[1], zhp1 = r[2], ob = r[3];
+    double z_cosmo = za;
+    if (!LIN && PM1) {
+      z_cosmo = fma(za, st > 0.0 ? r_pos : r_neg, c0);
+    } else if (!LIN && d.has_vstep) {
+      const double z_pec = (v100 * st) / d.c;
+      z_cosmo = -1.0 + za / (1.0 + z_pec);
+    }
+    if (!FAST && cf_stream_segment(cf_stream_node(z_cosmo, d.n_grid, d.inv_step, d.z_max), sa.n_seg) != s) return;
+    const double off_i = LIN ? off + lin * st : off;
+    out[(unsigned)row] = ob - off_i - fma_vsv(log10_tab(zhp1 * hermite_fast(T, z_cosmo), log_tab), 5.0, 25.0);
+  };
+  // two records in flight, as in sn_fast_loop (the first, {ra, rowa} of record j, fetched by the caller ahead of the table
+  // build); the arrays carry CF_STREAM_REC_SLACK spare entries
+  // (unsigned indices: scalar base + 32-bit lane offset, no per-lane 64-bit pointers held across the segment loop)
+  const d4* __restrict__ rec = reinterpret_cast<const d4*>(sa.rec);
+  const int32_t* __restrict__ rows = sa.row;
+  // No look-ahead past the segment's last record: a load nobody consumes would make the next segment's table stores wait for
+  // it, and with it (one counter for loads and stores) for every residual store of this segment.
+  d4 rb = ra;
+  int rowb = rowa;
+  while (j < end) {
+    if (j + 64 < end) {
+      rb = rec[j + 64];
+      rowb = rows[j + 64];
+    }
+    one_sn(ra, rowa);
+    j += 64;
+    if (j >= end) break;
+    if (j + 64 < end) {
+      ra = rec[j + 64];
+      rowa = rows[j + 64];
+    }
+    one_sn(rb, rowb);
+    j += 64;
+  }
+}
+
+template <int MODEL, int FDE>
+__global__ void __launch_bounds__(64 * CF_STREAM_WAVES, 4)
+walker_stream_kernel(cf_walker_args d, cf_stream_args sa, const double* __restrict__ theta, int64_t W, double* __restrict__ delta,
+                     d2* __restrict__ bao_nodes, double* __restrict__ theta_copy) {
+  __shared__ __align__(16) d2 win_all[CF_STREAM_WAVES][CF_STREAM_WIN];
+  // the two reduction tables, shared by the workgroup's walkers: EVERY wave stores the whole table (the same bits to the same
+  // place) before its own first read, so no wave waits for another
+  __shared__ __align__(16) d2 log_tab[64];
+  __shared__ double exp2_tab[64];
+
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t w = (int64_t)blockIdx.x * CF_STREAM_WAVES + wv;
+  if (w >= W) return;
+  d2* const win = win_all[wv];
+  constexpr bool POWER_LAW = FDE == CF_FDE_WCDM_D || FDE == CF_FDE_CPL_D;
+  const int G = d.n_grid;
+  const ThetaRow th{theta[w * d.ndim + (lane < d.ndim ? lane : 0)]};
+  if (theta_copy && lane < d.ndim) theta_copy[w * d.ndim + lane] = th.v;
+  log_tab[lane] = reinterpret_cast<const d2*>(d.log10_tab)[lane];  // (the host launches this form only with an SN block)
+  if (POWER_LAW) exp2_tab[lane] = d.exp2_tab[lane];
+  // the walker's scalars are the same in every lane: into scalar registers, or they hold ~40 vector registers across the loop
+  WalkerCosmo wc = make_cosmo(d, th);
+  wc.H0 = uniform_f64(wc.H0);
+  wc.Om = uniform_f64(wc.Om);
+  wc.w0 = uniform_f64(wc.w0);
+  wc.wa = uniform_f64(wc.wa);
+  wc.Or = uniform_f64(wc.Or);
+  wc.Obc = uniform_f64(wc.Obc);
+  wc.Ode = uniform_f64(wc.Ode);
+  wc.Onu = uniform_f64(wc.Onu);
+  const double off = uniform_f64(slot_get(d, CF_P_OFFSET_D, th));
+  const double v100 = uniform_f64(100 * slot_get(d, CF_P_V_D, th));
+  const double lin = d.lin_in_rec ? uniform_f64(slot_get(d, CF_P_LIN_D, th)) : 0.0;
+  const double c_over_H0 = uniform_f64(wc.c / wc.H0);
+  double* const out = delta + w * d.n_ld;
+  for (int i = d.n_sn + lane; i < d.n_ld; i += 64) out[i] = 0.0;  // zero padding of the solve's tiles, as in sn_fast_loop
+  // sn_fast_loop's PM1 factors: z_cosmo = fma(za, r, c0)
+  double r_pos = 1.0, r_neg = 1.0, c0 = 0.0;
+  if (d.step_pm1 && d.has_vstep) {
+    r_pos = uniform_f64(1.0 / (1.0 + v100 / d.c));
+    r_neg = uniform_f64(1.0 / (1.0 + (-v100) / d.c));
+    c0 = -1.0;
+  }
+  // one wave-uniform test: do this walker's SNe stay in the windows they were packed for?  (NaN fails it.)
+  double a_pec;
+  const double shift = cf_stream_shift_bound(v100, sa.max_step, sa.zp1_max, d.c, d.inv_step, &a_pec);
+  const bool fast = a_pec < 0.5 && shift <= (double)CF_STREAM_GUARD_NODES;
+  DistTable T;
+  T.G = G;
+  T.chs = 4;
+  T.step = d.step;
+  T.inv_step = d.inv_step;
+  T.inv_last = d.inv_last;
+  T.z_max = d.z_max;
+  // lane v: the interval sum of segment v and the boundary interval in front of it (what walker_fast_kernel forms from
+  // wave_pub[v - 1], wave_pub[v]); zero until built.  prev_last: dh of the last node of the segment before.
+  double seg_sum = 0.0, seg_bnd = 0.0, prev_last = 0.0;
+  wave_lds_sync();
+#pragma unroll 1
+  for (int s = 0; s < sa.n_seg; ++s) {
+    const int g0 = (64 * s + lane) * 8;
+    // this segment's first SN record: the load flies while the segment is built
+    const unsigned sn_j = (unsigned)((fast ? sa.seg_off[s] : 0) + lane), sn_end = (unsigned)(fast ? sa.seg_off[s + 1] : d.n_sn);
+    d4 sn_r = (d4){1.0, 1.0, 1.0, 0.0};
+    int sn_row = 0;
+    if (sn_j < sn_end) {
+      sn_r = reinterpret_cast<const d4*>(sa.rec)[sn_j];
+      sn_row = sa.row[sn_j];
+    }
+    double nu_pre[8], ln_pre[8], dh[8], loc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      nu_pre[k] = MODEL == CF_EZ_PHYSICAL_D ? d.nu_sw[k * CF_TPB_A + 64 * s + lane] : -1.0;
+      ln_pre[k] = POWER_LAW ? d.ln_sw[k * CF_TPB_A + 64 * s + lane] : -1.0;
+    }
+    const int wave_last = CF_STREAM_SEG * s + CF_STREAM_SEG - 1;
+    const double run = wave_last < G - 1 ? chunk_eval<MODEL, FDE, 8, false>(d, wc, c_over_H0, g0, lane, nu_pre, ln_pre, exp2_tab, dh, loc)
+                                         : chunk_eval<MODEL, FDE, 8, true>(d, wc, c_over_H0, g0, lane, nu_pre, ln_pre, exp2_tab, dh, loc);
+    const double incl = wave_inclusive_scan(run);
+    const double first_dh = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(dh[0])),
+                                             __builtin_amdgcn_readfirstlane(__double2loint(dh[0])));
+    const double tot = readlane_f64(incl, 63), last_dh = readlane_f64(dh[7], 63);
+    // the carry into this segment: the expression tree of build_distance_table_regs with `wave` = s.  The boundary interval
+    // in front of segment v has the same operands whenever it is formed, so lane v forms it once, when segment v is built.
+    if (lane == s) {
+      seg_sum = tot;
+      if (s >= 1) {
+        const int gb = s * 64 * 8;
+        const double zb = gb == G - 1 ? d.z_max : (double)gb * d.step;
+        seg_bnd = (prev_last + first_dh) / 2 * (zb - (double)(gb - 1) * d.step);
+      }
+    }
+    prev_last = last_dh;
+    double term = 0.0;
+    if (lane < CF_STREAM_MAX_SEGS) {
+      term = lane < s ? seg_sum : 0.0;
+      if (lane >= 1) term += (lane <= s && lane * 64 * 8 < G) ? seg_bnd : 0.0;
+    }
+    term += dpp_move<0x111, 0xF>(term);  // row_shr:1
+    term += dpp_move<0x112, 0xF>(term);  // row_shr:2
+    term += dpp_move<0x114, 0xF>(term);  // row_shr:4 -> lane 7 holds lanes 0..7
+    const double carry = (incl - run) + readlane_f64(term, 7);
+    const int base = CF_STREAM_Q0 + 8 * lane + (lane >> 1);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (g0 + k < G) win[base + k] = (d2){loc[k] + carry, dh[k]};
+    if (!(lane & 1) && g0 < G) win[base - 1] = (d2){loc[0] + carry, dh[0]};  // hermite_fast reads node i + 1 behind node i
+    wave_lds_sync();
+    // node g of the window's range sits at entry g + g / 16 - (512 s - 64) * 17 / 16
+    T.tab = win + (CF_STREAM_Q0 - (CF_STREAM_SEG / 16 * 17) * s);
+    for (int e = lane; e < CF_BAO_NODES * d.n_aux; e += 64) {  // each BAO / growth node from the segment that built it
+      const int k = e / CF_BAO_NODES, o = e % CF_BAO_NODES;
+      const int g = d.bao_base[k] + o;
+      if (min(g / CF_STREAM_SEG, sa.n_seg - 1) == s) bao_nodes[(w * d.n_aux + k) * CF_BAO_NODES + o] = T.at(g);
+    }
+    // (the guard as a template argument: the loop of the walkers that pass it carries none of the slow path's tests)
+#define CF_STREAM_SN(PM1, LIN, LINV, RP, RN, C0)                                                                                  \
+  (fast ? sn_stream_segment<PM1, LIN, true>(d, sa, T, log_tab, out, off, v100, LINV, RP, RN, C0, s, sn_j, sn_end, sn_r, sn_row)  \
+        : sn_stream_segment<PM1, LIN, false>(d, sa, T, log_tab, out, off, v100, LINV, RP, RN, C0, s, sn_j, sn_end, sn_r, sn_row))
+    if (d.lin_in_rec) CF_STREAM_SN(false, true, lin, 1.0, 1.0, 0.0);
+    else if (d.step_pm1) CF_STREAM_SN(true, false, 0.0, r_pos, r_neg, c0);
+    else CF_STREAM_SN(false, false, 0.0, 1.0, 1.0, 0.0);
+#undef CF_STREAM_SN
+    if (s + 1 < sa.n_seg) {  // the segment's last CF_STREAM_HALO nodes become the next window's halo
+      constexpr int TAIL = CF_STREAM_SEG / 16 * 17, NH = CF_STREAM_Q0;
+      const d2 h0 = win[TAIL + lane];
+      const d2 h1 = win[TAIL + 64 + (lane < NH - 64 ? lane : 0)];
+      wave_lds_sync();
+      win[lane] = h0;
+      if (lane < NH - 64) win[64 + lane] = h1;
+    }
+  }
+}
+
 // H(z) at a Gauss-Legendre node of the compressed-CMB distances (small_blocks_kernel evaluates it 2 n_gl times per walker: this is
 // where that kernel's instructions go, and it is bound by the instructions it issues -- profiles/NOTES_r04.md).  E^2 as e2_of_z
 // writes it, with sqrt_pos / div_pos (the library's bits) and, for the power-law dark-energy forms, ONE table-driven exp of
@@ -1554,6 +1762,7 @@ __global__ void hz_kernel(cf_dev_desc d, const double* __restrict__ theta, const
 #define CF_INSTANTIATE_WALKER(M, F)                                                                              \
   template __global__ void walker_kernel<M, F>(cf_dev_desc, const double*, int64_t, double*, double*, double*, d2*, d2*); \
   template __global__ void walker_fast_kernel<M, F>(cf_walker_args, const double*, int64_t, double*, d2*, double*, int, int);     \
+  template __global__ void walker_stream_kernel<M, F>(cf_walker_args, cf_stream_args, const double*, int64_t, double*, d2*, double*); \
   template __global__ void small_blocks_kernel<M, F, 16, 1>(cf_dev_desc, const double*, int64_t, const d2*, double*, double*, \
                                                             double*);                                                      \
   template __global__ void small_blocks_kernel<M, F, 64, 1>(cf_dev_desc, const double*, int64_t, const d2*, double*, double*, \

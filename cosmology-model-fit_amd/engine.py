@@ -438,6 +438,15 @@ class LikelihoodEngine:
         L.check(L.lib().cf_resid_sigma(self._h, L.RESID_BLOCKS[block], _ptr(out)))
         return out
 
+    def walker_form(self, W: int) -> int:
+        """Which form of the per-walker kernel a batch of W walkers runs through chi_squared / log_likelihood /
+        log_probability / eval_device: 0 = one workgroup per walker, 1 = streaming (one wave per walker, large batches;
+        the same bits), 2 = the generic kernel.  CF_TUNE walker_stream=0|1 forces the choice between 0 and 1."""
+        rc = L.lib().cf_walker_form(self._h, int(W))
+        if rc < 0:
+            L.check(rc)
+        return rc
+
     def enable_timing(self, slots=1, stride=1):
         """Keep HIP-event timings of the last `slots` timed evaluations (0 = off); only every `stride`-th evaluation is timed."""
         L.check(L.lib().cf_enable_timing(self._h, int(slots)))

@@ -395,6 +395,10 @@ int cf_kernel_ms(cf_handle* h, int64_t call, float t[2]);
 /* the same with the per-walker stage split: t[0] = walker_kernel, t[1] = small-block (+ growth) kernels, t[2] = solve kernel */
 int cf_kernel_ms3(cf_handle* h, int64_t call, float t[3]);
 int cf_last_kernel_ms(cf_handle* h, float t[2]);
+/* Which form of the per-walker kernel cf_eval / cf_eval_device run for a batch of W walkers: 0 = one workgroup per walker,
+ * 1 = streaming (one wave per walker, large batches; the same bits), 2 = the generic kernel.  Negative: an error code.
+ * CF_TUNE walker_stream=0|1 forces the choice between 0 and 1 where both are allowed. */
+int cf_walker_form(cf_handle* h, int64_t W);
 
 /* ---- stand-alone operators with the reference's signatures (host buffers) ---- */
 /* out[k] = Hermite(xq[k]; x, y, y_prime), linear extrapolation outside   interpolator.py:117-119 */
