@@ -199,6 +199,16 @@ class cf_mock_set(C.Structure):
                 ("g_sn", C.c_void_p), ("g_bao", C.c_void_p), ("g_cmb", C.c_void_p), ("c", C.c_void_p)]
 
 
+CF_INFL_NCOL, CF_INFL_CHUNK = 5, 4096
+# cf_infl_col of include/cosmofit.h, in column order
+INFL_COLUMNS = ("chi2", "max_z", "max_z_index", "max_drop", "max_drop_index")
+
+
+class cf_infl_out(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("_pad", C.c_int32),
+                ("g", C.c_void_p), ("contrib", C.c_void_p), ("z", C.c_void_p), ("loo", C.c_void_p), ("sample", C.c_void_p)]
+
+
 class cf_info(C.Structure):
     _fields_ = [
         ("n_sn", C.c_int64), ("n_sn_pad", C.c_int64), ("packed_chol_bytes", C.c_int64),
@@ -294,6 +304,19 @@ EXPORTS = {
     "cf_mock_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _I32, C.POINTER(cf_mock_set), _VP, _I64, _VP, _I32, _VP]),
     "cf_mock_set_chunk": (C.c_int, [_VP, _I64]),
     "cf_mock_normals": (C.c_int, [C.c_uint64, _I64, _I64, _I32, _VP, _VP]),
+    "cf_prec_create": (C.c_int, [_VP, _I64, _I64, _I32, C.POINTER(_VP)]),
+    "cf_prec_create_inv": (C.c_int, [_VP, _I64, _I64, _I32, C.POINTER(_VP)]),
+    "cf_prec_destroy": (None, [_VP]),
+    "cf_prec_diag": (C.c_int, [_VP, _VP]),
+    "cf_prec_apply_device": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _VP]),
+    "cf_selftest_prec_host": (C.c_int, [_VP, _I64, _I64, _VP, _VP]),
+    "cf_infl_device": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _I32, _VP, _I32, C.POINTER(cf_infl_out), C.POINTER(cf_resid_acc),
+                                 C.POINTER(cf_resid_acc), _VP]),
+    "cf_infl": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _I32, _VP, _I32, C.POINTER(cf_infl_out), C.POINTER(cf_resid_acc),
+                          C.POINTER(cf_resid_acc)]),
+    "cf_infl_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _VP, _I64, _I32, _VP, _I32,
+                                     C.POINTER(cf_infl_out), C.POINTER(cf_resid_acc), C.POINTER(cf_resid_acc)]),
+    "cf_infl_set_chunk": (C.c_int, [_VP, _I64]),
 }
 
 

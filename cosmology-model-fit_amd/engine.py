@@ -279,6 +279,25 @@ class LikelihoodEngine:
             L.lib().cf_destroy(self._h)
             self._h = C.c_void_p()
         self.__dict__.pop("_mock_factor_dev", None)  # mocks.MockSet's device copy of the SN factor
+        for prec in self.__dict__.pop("_precision", {}).values():  # the precision matrices of ``precision()``
+            prec.close()
+
+    def precision(self, block="sn"):
+        """The block's precision matrix K = C^-1 on the engine's device (``influence.Precision`` over a ``cf_prec``), built at the
+        first call and kept until ``close()``: from the Cholesky factor the engine was built with for "sn" (K = Linv^T Linv in
+        extended precision on the host), the inverse covariance itself, symmetrised, for "bao"."""
+        from . import influence
+
+        if block not in L.RESID_BLOCKS:
+            raise ValueError(f"block must be one of {sorted(L.RESID_BLOCKS)}")
+        cache = self.__dict__.setdefault("_precision", {})
+        if block not in cache:
+            src = self.mock_data["sn_chol" if block == "sn" else "bao_inv_cov"]
+            if src is None or self.model_info["quasar"]:
+                raise ValueError(f"this engine has no {block.upper()} block to take a precision matrix from")
+            info = self.info()
+            cache[block] = influence.Precision(src, device=int(info["device"]), from_factor=block == "sn")
+        return cache[block]
 
     def __del__(self):
         try:

@@ -447,6 +447,17 @@ class ShardedEnsemble:
         eng = fit_report.engine_of(self.log_prob_fn, engine, "ShardedEnsemble.fit_report")
         return fit_report.chain_report(eng, self.get_chain(discard=discard, thin=thin, flat=True), **kw)
 
+    def influence(self, discard: int = 0, thin: int = 1, engine=None, **kw) -> dict:
+        """``influence.chain_report(engine, get_chain(discard, thin, flat=True), **kw)``: which data carry the chi^2 of the
+        stored samples -- per datum the posterior mean and scatter of its leave-one-out z-score and of its share of chi^2,
+        computed on the device.  engine: as for ``fit_report``.  Keywords: block, thresholds."""
+        from . import fit_report, influence
+
+        if "weights" in kw:
+            raise TypeError("an ensemble's samples carry no weights")
+        eng = fit_report.engine_of(self.log_prob_fn, engine, "ShardedEnsemble.influence")
+        return influence.chain_report(eng, self.get_chain(discard=discard, thin=thin, flat=True), **kw)
+
     def mean_path(self, discard: int = 0) -> torch.Tensor:
         """The walker mean per stored step, [n, ndim] on the device: the black line of the reference's trace plot
         (corner_plot.py:30)."""

@@ -392,6 +392,17 @@ class DeviceNestedSampler:
         pts, w = self._posterior_on_device()
         return fit_report.chain_report(eng, pts, weights=w, **kw)
 
+    def influence(self, engine=None, **kw) -> dict:
+        """``influence.chain_report`` of the posterior points with their weights exp(log_w): which data carry the chi^2 of
+        the posterior.  engine: as for ``fit_report``.  Keywords: block, thresholds."""
+        from . import fit_report, influence
+
+        if "weights" in kw:
+            raise TypeError("the nested sampler passes its own posterior weights")
+        eng = fit_report.engine_of(self.log_likelihood, engine, "DeviceNestedSampler.influence")
+        pts, w = self._posterior_on_device()
+        return influence.chain_report(eng, pts, weights=w, **kw)
+
     def mean_std(self):
         """``marginals.weighted_mean_std`` of the same points and weights: (mean [ndim], std [ndim]) on the device, what the
         nautilus scripts print per parameter (getdist's ``mean`` and ``std``)."""

@@ -1045,6 +1045,84 @@ int cf_mock_set_chunk(cf_handle* h, int64_t rows);
  * in pieces.  CF_ERR_INVALID: k0 < 0, K < 0, n < 1, (k0 + K) n > 2^62, a null d_out with K > 0.  K = 0 is a no-op. */
 int cf_mock_normals(uint64_t key, int64_t k0, int64_t K, int32_t n, double* d_out, void* hip_stream);
 
+/* ---- Which data carry a chi^2: per-datum attribution and leave-one-out residuals (csrc/cosmofit_infl.hip; the driver is
+ * cosmology-model-fit_amd/influence.py) ----------------------------------------------------------------------------------------
+ * The reference reads a Delta chi^2 between two models as a statement about individual data (README: the supernovae on either side
+ * of z_turn).  With a dense covariance the raw pull r_i / sqrt(C_ii) of the fit report is no test statistic; what is one comes
+ * from a single vector per row, g = K r with K = C^-1 the precision matrix of the block:
+ *   contrib_i = r_i g_i            sum_i contrib_i = chi^2, so contrib_i(theta_A) - contrib_i(theta_B) splits a Delta chi^2 exactly
+ *   loo_i     = g_i / K_ii         datum i minus its prediction from all the others; its error is 1 / sqrt(K_ii)
+ *   z_i       = g_i / sqrt(K_ii)   the z-score of that leave-one-out residual
+ *   chi^2 without datum i = chi^2 - g_i^2 / K_ii (no refit of the covariance).
+ *
+ * cf_prec: K on one device.  cf_prec_create reads the LOWER triangle of the Cholesky factor L [n x n, row pitch ld] and forms
+ * K = Linv^T Linv on the host in extended precision from the extended-precision columns of the inverse (forward substitution
+ * with compensated sums; Linv is not rounded to double in between; K is rounded once).  cf_prec_create_inv takes the precision matrix itself [n x n, row pitch ld] (the BAO
+ * block's inverse covariance) and symmetrises it, (A + A^T) / 2; a datum whose diagonal entry is 0 is one the likelihood ignores
+ * (its row and column are zero): g, contrib, z and loo are 0 there.  Both upload K (zero-padded to a multiple of 16), diag K and
+ * 1 / sqrt(diag K).  cf_prec_diag copies diag K out [n] (no HIP call).  CF_ERR_INVALID: a null argument, n < 1 or > 32768,
+ * ld < n; CF_ERR_NOT_POSDEF: a factor with a diagonal entry that is not finite and > 0, an inverse covariance with a non-finite
+ * entry or a negative diagonal entry; CF_ERR_NO_DEVICE without a device.
+ *
+ * cf_prec_apply_device: the bare product d_g[s * g_pitch + j] = sum_i d_rows[s * pitch + i] K_ij for s < S, j < n on FP64 matrix
+ * cores; columns >= n and rows >= S of d_rows are never read, columns >= n of d_g never written.  The k loop is ascending with one
+ * accumulator per output, so a row of d_g depends on its row of d_rows and on K only: not on S, the row's position or the stream.
+ * A NaN or inf in a row stays in that row.  CF_ERR_INVALID: a null argument (S > 0), S < 0 or > 2^31 - 1, pitch or g_pitch < n.
+ *
+ * cf_infl_device: for every row of d_theta [S * ndim] the residual row of the accessor path (as cf_resid_device: chunks of at
+ * most CF_INFL_CHUNK rows into the handle's workspace), g = K r, and from it
+ *   out->g, contrib, z, loo [S * n] (each may be NULL), out->sample [S * CF_INFL_NCOL] (may be NULL; cf_infl_col):
+ *     chi2 = sum_i r_i g_i (lane-strided partials and a fixed butterfly), max_z = max_i |z_i| and its index, max_drop =
+ *     max_i g_i^2 / K_ii and its index (np.argmax's rule: the first NaN, else the first maximum);
+ *   acc_z: the running per-datum state of cf_resid_device (West's update, thresholds in units of sigma = 1) over the z rows;
+ *   acc_contrib: the same over the contrib rows, without thresholds (its n_thr must be 0).
+ *   A row's bits depend on theta only: not on S, its position, the chunking (cf_infl_set_chunk) or device / host pointers; the
+ *   accumulators give the same bits for every split of a chain into consecutive calls.  A non-finite theta entry gives NaN in
+ *   that row only, and the accumulators skip it.
+ * block: CF_RB_SN (r = the row's residual vector) or CF_RB_BAO (r = val - bao_theory).  d_w: NULL or [S], read by the accumulators.
+ *
+ * Checks, all before the first HIP call (cf_infl_check_args states them without a handle), all CF_ERR_INVALID: a quasar handle,
+ * a handle over several devices, a block the handle lacks, a null cf_prec, prec_n that is not the block's n, a cf_prec on
+ * another device than the handle, S < 0 or > 2^31 - 1, n_thr outside 0 .. CF_RESID_MAX_THR, a non-finite or negative threshold,
+ * an out whose struct_size does not match, an accumulator whose struct_size / n / n_thr do not match or with a null array,
+ * no output at all, and (S > 0) a null d_theta.  S = 0 is a no-op.
+ * Stream contract: that of cf_resid_device (the handle's ONE workspace).
+ * cf_infl: the same on host buffers (the accumulators' arrays host arrays too), synchronous, same bits. */
+#define CF_INFL_NCOL 5
+#define CF_INFL_CHUNK 4096
+enum cf_infl_col { CF_IS_CHI2 = 0, CF_IS_MAX_Z = 1, CF_IS_MAX_Z_IDX = 2, CF_IS_MAX_DROP = 3, CF_IS_MAX_DROP_IDX = 4 };
+typedef struct cf_prec cf_prec;
+typedef struct cf_infl_out {
+  int32_t struct_size; /* sizeof(cf_infl_out) as seen by the caller */
+  int32_t _pad;
+  double* g;           /* [S * n] K r */
+  double* contrib;     /* [S * n] r_i g_i */
+  double* z;           /* [S * n] g_i / sqrt(K_ii) */
+  double* loo;         /* [S * n] g_i / K_ii */
+  double* sample;      /* [S * CF_INFL_NCOL] */
+} cf_infl_out;
+
+int cf_prec_create(const double* L, int64_t n, int64_t ld, int32_t device, cf_prec** out);
+int cf_prec_create_inv(const double* inv_cov, int64_t n, int64_t ld, int32_t device, cf_prec** out);
+void cf_prec_destroy(cf_prec* p);
+int cf_prec_diag(cf_prec* p, double* out_n);
+int cf_prec_apply_device(cf_prec* p, const double* d_rows, int64_t pitch, int64_t S, double* d_g, int64_t g_pitch, void* hip_stream);
+/* The host half of cf_prec_create alone: K [n * n] and diag K [n] (either may be NULL) of the factor L.  No device needed. */
+int cf_selftest_prec_host(const double* L, int64_t n, int64_t ld, double* K_out, double* kdiag_out);
+int cf_infl_device(cf_handle* h, cf_prec* prec, const double* d_theta, int64_t S, const double* d_w, int32_t block,
+                   const double* thresholds, int32_t n_thr, cf_infl_out* out, cf_resid_acc* acc_z, cf_resid_acc* acc_contrib,
+                   void* hip_stream);
+int cf_infl(cf_handle* h, cf_prec* prec, const double* theta, int64_t S, const double* w, int32_t block, const double* thresholds,
+            int32_t n_thr, cf_infl_out* out, cf_resid_acc* acc_z, cf_resid_acc* acc_contrib);
+/* The argument rules above as host arithmetic on the facts of a handle (its n_sn, n_bao, whether it is a quasar handle, its
+ * number of devices, its device) and of a cf_prec (has_prec: non-null; its n and device).  No handle and no device needed. */
+int cf_infl_check_args(int64_t n_sn, int32_t n_bao, int32_t is_quasar, int32_t n_devices, int32_t handle_device, int32_t has_prec,
+                       int64_t prec_n, int32_t prec_device, const void* theta, int64_t S, int32_t block, const double* thresholds,
+                       int32_t n_thr, const cf_infl_out* out, const cf_resid_acc* acc_z, const cf_resid_acc* acc_contrib);
+/* Rows per chunk of the following cf_infl_device / cf_infl calls of this handle, 1 .. 65536; 0 restores CF_INFL_CHUNK.  The
+ * results do not depend on it: it exists so that tests can cross chunk boundaries with few rows. */
+int cf_infl_set_chunk(cf_handle* h, int64_t rows);
+
 #ifdef __cplusplus
 }
 #endif

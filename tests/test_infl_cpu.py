@@ -1,0 +1,313 @@
+"""CPU: everything of the attribution that needs no device -- the long-double restatement against the chi^2 the reference
+computed and against brute-force deletion of a datum, the host-side precision matrix of ``cf_prec_create``, the layout of
+``cf_infl_out``, the argument rules of ``cf_infl_device`` (stated without a handle by ``cf_infl_check_args``), and the keyword and
+ordering arithmetic of ``influence``."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import infl_reference as IR
+import infl_shapes as IS
+import resid_shapes as RS
+from conftest import ROOT, golden, load_pkg, synthetic_cov
+
+amd = load_pkg()
+L = amd._lib
+I = importlib.import_module("cosmology-model-fit_amd.influence")
+
+
+# ---- the restatement against the reference's own numbers -----------------------------------------------------------------------
+def _fixture_rows(case):
+    """(residual rows, the chi^2 the reference computed for them, g of the restatement)."""
+    g = golden(case)
+    if case == "sn_pantheon":  # the residual vectors of the first three thetas, synthetic covariance
+        rows = np.array([g[f"delta_{k}"] for k in range(3)])
+        return rows, g["chi2"][:3], IR.g_rows(np.linalg.cholesky(synthetic_cov(g["sigma"])), rows)
+    if case == "sn_union3_1":  # the fixture stores no residual vector: the project's numpy oracle restates the model
+        from oracle import oracle_np as onp
+        from test_oracle_golden import lk_sn_union3_1
+
+        lk = lk_sn_union3_1(g)
+        keep = np.isfinite(g["chi2"])
+        rows = np.array([onp.sn_parts(lk, t)[3] for t in g["thetas"][keep]])
+        return rows, g["chi2"][keep], IR.g_rows(np.linalg.cholesky(g["cov"]), rows)
+    rows = g["bao_val"][None, :] - g["theory"]  # the last three thetas
+    return rows, g["chi2"][-3:], IR.g_rows_inv(g["bao_inv_cov"], rows)
+
+
+@pytest.mark.parametrize("case", ["sn_union3_1", "sn_pantheon", "bao_desi_fs_lya"])
+def test_contributions_sum_to_the_chi2_the_reference_computed(case):
+    rows, chi2, g = _fixture_rows(case)
+    assert rows.shape[0] >= 3
+    got = (np.asarray(rows, dtype=IR.LD) * g).sum(axis=1)
+    err = np.abs(np.asarray(got / chi2 - 1, dtype=np.float64))
+    print(case, "sum_i r_i g_i against the fixture's chi2, largest relative error: %.2e" % err.max())
+    assert err.max() <= 1e-10
+
+
+# ---- the restatement against brute force ---------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def hard():
+    cov = IS.covariance(amd, IS.N_HARD)
+    chol = np.linalg.cholesky(cov)
+    r = IS.residual_rows(chol, 1, seed=4)[0]
+    K, bound = IR.precision(chol)
+    return dict(cov=cov, chol=chol, r=r, K=K, bound=bound, g=IR.g_rows(chol, r[None, :])[0])
+
+
+def test_leave_one_out_and_deletion_equal_brute_force(hard):
+    r, g, kd = np.asarray(hard["r"], dtype=IR.LD), hard["g"], np.diag(hard["K"])
+    chi2 = (r * g).sum()
+    worst_e = worst_c = 0.0
+    for i in (0, 128, IS.N_HARD - 1):
+        e_ref, chi2_ref = IR.deleted_problem(hard["cov"], r, i)
+        worst_e = max(worst_e, abs(float((g[i] / kd[i] - e_ref) / e_ref)))
+        worst_c = max(worst_c, abs(float((chi2 - g[i] ** 2 / kd[i] - chi2_ref) / chi2_ref)))
+    print("n = 257, hard_cov: e_i against the conditional mean %.2e, chi2 - g_i^2 / K_ii against the deleted problem %.2e (relative)"
+          % (worst_e, worst_c))
+    assert worst_e <= 1e-10 and worst_c <= 1e-10
+
+
+def test_the_two_routes_to_g_agree(hard):
+    """Two substitutions with the factor against the product with the long-double K: the restatement's own consistency."""
+    via_k = np.asarray(hard["r"], dtype=IR.LD) @ hard["K"]
+    scale = np.abs(hard["r"]) @ np.asarray(hard["bound"], dtype=np.float64)
+    assert float(np.max(np.abs(np.asarray(via_k - hard["g"], dtype=np.float64)) / scale)) <= 1e-15
+
+
+def test_attribution_totals_and_cumulative_sum():
+    rng = np.random.default_rng(8)
+    cov = IS.covariance(amd, 65)
+    chol = np.linalg.cholesky(cov)
+    ra, rb = IS.residual_rows(chol, 5, seed=2), IS.residual_rows(chol, 5, seed=3)
+    ca, cb = ra * IR.g_rows(chol, ra), rb * IR.g_rows(chol, rb)
+    order = rng.permutation(65)
+    delta, cum, total = IR.attribution(ca[0], cb[0], order)
+    chi2_a, chi2_b = ca.sum(axis=1), cb.sum(axis=1)
+    assert abs(float(total - (chi2_a[0] - chi2_b[0]))) <= 1e-15 * float(chi2_a[0] + chi2_b[0])
+    assert abs(float(cum[-1] - total)) <= 1e-15 * float(np.abs(delta).sum())
+    assert np.array_equal(cum, np.cumsum(delta[order]))
+    delta, cum, total = IR.attribution(ca, cb, order)  # paired rows: the mean over the pairs
+    assert abs(float(total - (chi2_a - chi2_b).mean())) <= 1e-15 * float((chi2_a + chi2_b).mean())
+    assert abs(float(cum[-1] - total)) <= 1e-15 * float(np.abs(delta).sum())
+
+
+# ---- the host half of cf_prec_create --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [1, 2, 17, 64, 65, 255, 256, IS.N_HARD])
+def test_host_precision_matrix_is_rounded_once(n):
+    """K entrywise against the restatement's long-double K, within 4 eps of (|Linv|^T |Linv|)_ij: sizes around the 16-wide padding
+    and the 256 at which the host work is spread over threads, ``hard_cov`` at n = 257.  (On ``hard_cov`` a plain
+    extended-precision substitution is 6.5 eps from a 160-bit K and the restatement 1.5 eps; the library's compensated one
+    1.2 eps.)"""
+    chol = np.linalg.cholesky(IS.covariance(amd, n))
+    dirty = chol + np.triu(np.full((n, n), np.nan), 1)  # the strict upper triangle is never read
+    K, kd = IS.host_precision(L, amd.lib(), dirty)
+    want, bound = IR.precision(chol)
+    err = np.asarray(np.abs(K - want) / bound, dtype=np.float64)
+    print("n = %d: K against the long-double restatement, largest error %.2f eps of (|Linv|^T |Linv|)_ij" % (n, err.max() / IR.EPS))
+    assert err.max() <= 4 * IR.EPS
+    assert np.array_equal(K, K.T) and np.array_equal(kd, np.diag(K))
+
+
+def test_prec_entry_points_refuse_bad_arguments():
+    lib = amd.lib()
+    inv, notpd = -1, -4
+    p, eye = C.c_void_p(), np.eye(4)
+    assert lib.cf_prec_create(None, 4, 4, 0, C.byref(p)) == inv and b"null matrix" in lib.cf_last_error()
+    assert lib.cf_prec_create(eye.ctypes.data, 4, 4, 0, None) == inv
+    assert lib.cf_prec_create(eye.ctypes.data, 0, 4, 0, C.byref(p)) == inv and lib.cf_prec_create(eye.ctypes.data, 4, 3, 0, C.byref(p)) == inv
+    bad = eye.copy()
+    bad[2, 2] = 0.0
+    assert lib.cf_prec_create(bad.ctypes.data, 4, 4, 0, C.byref(p)) == notpd and b"bad pivot" in lib.cf_last_error()
+    assert lib.cf_selftest_prec_host(bad.ctypes.data, 4, 4, None, None) == notpd
+    bad = eye.copy()
+    bad[1, 3] = np.inf
+    assert lib.cf_prec_create_inv(bad.ctypes.data, 4, 4, 0, C.byref(p)) == notpd
+    bad = eye.copy()
+    bad[1, 1] = -1.0
+    assert lib.cf_prec_create_inv(bad.ctypes.data, 4, 4, 0, C.byref(p)) == notpd
+    assert lib.cf_prec_create_inv(None, 4, 4, 0, C.byref(p)) == inv
+    if lib.cf_device_count() == 0:
+        assert lib.cf_prec_create(eye.ctypes.data, 4, 4, 0, C.byref(p)) == -2 and b"no HIP device" in lib.cf_last_error()
+    assert not p.value
+    assert lib.cf_prec_diag(None, None) == inv and lib.cf_prec_apply_device(None, None, 4, 1, None, 4, None) == inv
+    lib.cf_prec_destroy(None)
+
+
+# ---- the C side ----------------------------------------------------------------------------------------------------------------
+def test_out_layout_matches_c(tmp_path):
+    fields = [name for name, _ in L.cf_infl_out._fields_]
+    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "cosmofit.h"\nint main(){printf("%zu %d %d", sizeof(cf_infl_out), ' \
+           'CF_INFL_NCOL, CF_INFL_CHUNK);' + \
+           "".join(f'printf(" %zu", offsetof(cf_infl_out, {f}));' for f in fields) + \
+           'printf(" %d %d %d %d %d", CF_IS_CHI2, CF_IS_MAX_Z, CF_IS_MAX_Z_IDX, CF_IS_MAX_DROP, CF_IS_MAX_DROP_IDX);return 0;}'
+    src, exe = tmp_path / "out.c", tmp_path / "out"
+    src.write_text(prog)
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    vals = list(map(int, subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()))
+    assert vals[:3] == [C.sizeof(L.cf_infl_out), L.CF_INFL_NCOL, L.CF_INFL_CHUNK]
+    nf = len(fields)
+    for f, off in zip(fields, vals[3:3 + nf]):
+        assert getattr(L.cf_infl_out, f).offset == off, f
+    assert vals[3 + nf:] == [0, 1, 2, 3, 4] and len(L.INFL_COLUMNS) == L.CF_INFL_NCOL and L.INFL_COLUMNS == IR.COLUMNS
+    assert amd.lib().cf_abi_version() == 11  # appended entry points: the descriptor did not change
+
+
+def _check(n_sn=100, n_bao=13, quasar=0, n_devices=1, hdev=0, has_prec=1, prec_n=None, pdev=0, theta=1, S=5, block=L.CF_RB_SN,
+           thr=(2.0, 3.0), n_thr=None, out="sample", acc_z=None, acc_c=None):
+    """cf_infl_check_args with non-null dummies (the function dereferences thresholds, out and the accumulators only)."""
+    t = np.asarray(thr, dtype=np.float64)
+    o = None
+    if out is not None:
+        o = L.cf_infl_out()
+        o.struct_size = C.sizeof(L.cf_infl_out)
+        if out:
+            setattr(o, out, 1)
+    if prec_n is None:
+        prec_n = n_sn if block == L.CF_RB_SN else n_bao
+    return amd.lib().cf_infl_check_args(n_sn, n_bao, quasar, n_devices, hdev, has_prec, prec_n, pdev, theta or None, S, block,
+                                        t.ctypes.data if t.size else None, t.size if n_thr is None else n_thr,
+                                        None if o is None else C.byref(o), acc_z, acc_c)
+
+
+def test_argument_errors_are_reported_before_any_device_work():
+    lib = amd.lib()
+    inv = -1
+    said = set()
+
+    def refused(rc, words):
+        msg = lib.cf_last_error()
+        assert rc == inv and words in msg, (rc, msg)
+        said.add(msg)
+
+    assert _check() == 0
+    refused(_check(quasar=1), b"quasar")
+    refused(_check(n_devices=2), b"several devices")
+    refused(_check(block=L.CF_RB_SN, n_sn=0), b"no SN block")
+    refused(_check(block=L.CF_RB_BAO, n_bao=0), b"no BAO block")
+    refused(_check(block=2), b"block must be")
+    refused(_check(has_prec=0), b"null cf_prec")
+    refused(_check(prec_n=99), b"cf_prec.n is not")
+    refused(_check(block=L.CF_RB_BAO, prec_n=100), b"cf_prec.n is not")
+    refused(_check(pdev=1), b"another device")
+    refused(_check(n_thr=5, thr=(1.0,) * 5), b"n_thr must be in 0..4")
+    assert len(said) == 9  # each refusal with its own message
+    assert _check(block=-1) == inv and _check(S=-1) == inv and _check(S=2**31) == inv and _check(n_thr=-1) == inv
+    assert _check(thr=(), n_thr=2) == inv and _check(thr=(1.0, np.nan)) == inv and _check(thr=(-1.0,)) == inv
+    assert _check(thr=(), n_thr=0) == 0                        # no thresholds is accepted
+    assert _check(theta=0) == inv and b"null theta" in lib.cf_last_error()
+    assert _check(out=None) == inv and b"no output" in lib.cf_last_error()
+    assert _check(out="") == inv and b"no output" in lib.cf_last_error()
+    assert _check(theta=0, S=0) == 0                           # no rows: a no-op, nothing is read
+    for name in ("g", "contrib", "z", "loo"):
+        assert _check(out=name) == 0
+    o = L.cf_infl_out()
+    o.struct_size, o.sample = C.sizeof(L.cf_infl_out) - 8, 1
+    assert lib.cf_infl_check_args(100, 13, 0, 1, 0, 1, 100, 0, 1, 5, 0, None, 0, C.byref(o), None, None) == inv
+    az, _ = RS.host_acc(L, 100, 2)
+    ac, _ = RS.host_acc(L, 100, 0)
+    assert _check(out=None, acc_z=C.byref(az)) == 0 and _check(out=None, acc_c=C.byref(ac)) == 0
+    assert _check(acc_z=C.byref(az), acc_c=C.byref(ac)) == 0
+    assert _check(acc_z=C.byref(az), thr=(1.0,)) == inv and b"acc_z.n_thr differs" in lib.cf_last_error()
+    assert _check(acc_c=C.byref(az)) == inv and b"acc_contrib.n_thr must be 0" in lib.cf_last_error()
+    assert _check(acc_z=C.byref(az), block=L.CF_RB_BAO) == inv  # 100 data, the BAO block has 13
+    for field in ("w_sum", "mean", "m2", "exceed", "n_used", "n_skipped"):
+        bad, _ = RS.host_acc(L, 100, 2)
+        setattr(bad, field, None)
+        assert _check(acc_z=C.byref(bad)) == inv, field
+    bad, _ = RS.host_acc(L, 100, 2)
+    bad.struct_size -= 8
+    assert _check(acc_z=C.byref(bad)) == inv
+    # a null handle, with or without a device
+    assert lib.cf_infl_device(None, None, None, 0, None, 0, None, 0, None, None, None, None) == inv
+    assert lib.cf_infl(None, None, None, 0, None, 0, None, 0, None, None, None) == inv
+    assert lib.cf_infl_set_chunk(None, 32) == inv
+
+
+# ---- influence's host arithmetic -----------------------------------------------------------------------------------------------
+class _FakeEngine:
+    """An engine of 3 parameters and 6 SNe (redshifts out of order) whose contributions are functions of the row."""
+    ndim, n_sn, n_bao = 3, 6, 0
+    model_info = dict(quasar=False, multi_device=False)
+    sn_z = np.array([0.5, 0.1, 0.3, 0.1, 0.9, 0.2])
+    bao_z = None
+
+
+def _fake_rows(engine, theta, block="sn", want=I.WANT):
+    contrib = theta.sum(dim=1)[:, None] * torch.arange(1, 7, dtype=torch.float64)[None, :] ** 2
+    return dict(contrib=contrib, sample=dict(chi2=contrib.sum(dim=1)))
+
+
+@pytest.fixture
+def host_rows(monkeypatch):
+    monkeypatch.setattr(I.F.chain_stats, "_on_device", lambda x, what: x)
+    monkeypatch.setattr(I, "_to_device", lambda a: torch.from_numpy(np.ascontiguousarray(a)))
+    monkeypatch.setattr(I, "rows", _fake_rows)
+
+
+def test_attribution_ordering_and_totals_on_a_stub(host_rows):
+    eng = _FakeEngine()
+    a, b = np.array([1.0, 2.0, 3.0]), np.array([0.5, 0.5, 1.0])
+    out = I.attribution(eng, a, b)
+    sq = np.arange(1, 7) ** 2.0
+    assert np.array_equal(out["delta"], 6.0 * sq - 2.0 * sq) and np.array_equal(out["delta_std"], np.zeros(6))
+    assert np.array_equal(out["order"], [1, 3, 5, 2, 0, 4])           # ascending redshift, the first of equals first
+    assert np.array_equal(out["redshift"], [0.1, 0.1, 0.2, 0.3, 0.5, 0.9])
+    assert np.array_equal(out["cumulative"], np.cumsum(out["delta"][out["order"]]))
+    assert out["total"] == 4.0 * sq.sum() == out["cumulative"][-1] and out["chi2_a"][0] - out["chi2_b"][0] == out["total"]
+    given = I.attribution(eng, torch.from_numpy(a), torch.from_numpy(b), order=[5, 4, 3, 2, 1, 0])
+    assert np.array_equal(given["cumulative"], np.cumsum(out["delta"][::-1])) and np.array_equal(given["redshift"], eng.sn_z[::-1])
+    # paired chain rows: the mean and scatter over the pairs
+    A, B = np.array([[1.0, 2.0, 3.0], [2.0, 2.0, 2.0]]), np.array([[0.5, 0.5, 1.0], [1.0, 1.0, 1.0]])
+    pair = I.attribution(eng, A, B)
+    assert np.array_equal(pair["delta"], 0.5 * (4.0 + 3.0) * sq) and np.array_equal(pair["delta_std"], 0.5 * sq)
+    assert np.array_equal(pair["total_rows"], [4.0 * sq.sum(), 3.0 * sq.sum()]) and pair["total"] == 3.5 * sq.sum()
+    with pytest.raises(ValueError, match="permutation"):
+        I.attribution(eng, a, b, order=[0, 1, 2, 3, 4, 4])
+    with pytest.raises(ValueError, match="same number of paired rows"):
+        I.attribution(eng, A, b)
+    with pytest.raises(ValueError, match=r"theta \[3\] or \[S, 3\]"):
+        I.attribution(eng, np.ones(4), np.ones(4))
+
+
+def test_keyword_and_argument_checks():
+    eng = _FakeEngine()
+    x = torch.zeros((5, 3), dtype=torch.float64)
+    with pytest.raises(TypeError, match="unexpected keyword.*center"):
+        I.chain_report(eng, x, center="mean")
+    with pytest.raises(ValueError, match="want must be among"):
+        I.rows(eng, x, want=("contrib", "pull"))
+    with pytest.raises(ValueError, match="MI355X"):
+        I.rows(eng, x)
+    with pytest.raises(ValueError, match="block must be one of"):
+        I.rows(eng, x, block="cc")
+    with pytest.raises(ValueError, match="no BAO block"):
+        I.rows(eng, x, block="bao")
+    with pytest.raises(ValueError, match="at most 4 thresholds"):
+        I.report(eng, x, thresholds=(1, 2, 3, 4, 5))
+    quasar = SimpleNamespace(model_info=dict(quasar=True, multi_device=False), ndim=3, n_sn=6, n_bao=0)
+    multi = SimpleNamespace(model_info=dict(quasar=False, multi_device=True), ndim=3, n_sn=6, n_bao=0)
+    with pytest.raises(ValueError, match="quasar engine"):
+        I.rows(quasar, x)
+    with pytest.raises(ValueError, match="several devices"):
+        I.attribution(multi, x, x)
+    with pytest.raises(ValueError, match="square matrix"):
+        I.Precision(np.ones((3, 4)))
+    assert amd.influence is I
+
+
+def test_samplers_refuse_weights_and_need_an_engine():
+    import chain_gloo_worker as cw
+
+    ens = cw.make_ensemble(24, (("stretch", 1.0),))
+    ens.run_mcmc(2)
+    with pytest.raises(TypeError, match="carry no weights"):
+        ens.influence(weights=torch.ones(48, dtype=torch.float64))
+    with pytest.raises(ValueError, match="needs the likelihood's engine"):
+        ens.influence()
