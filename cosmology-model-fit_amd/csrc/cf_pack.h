@@ -296,9 +296,12 @@ static void cf_invert_lower(const double* L, int64_t n, int64_t ld, int64_t n_pa
 // is one aligned 16-byte load from the row-major residual vector.
 static inline int64_t cf_inv_col(int64_t s2, int kq, int h) { return 8 * s2 + 2 * kq + h; }
 
+// row blocks (four 16-row tiles = 64 rows) of the packed inverse of an n-row factor
+static inline int cf_inv_rowblocks(int64_t n) { return (int)(((n + 15) / 16 + 3) / 4); }
+
 static void cf_pack_inverse(const double* L, int64_t n, int64_t ld, cf_host_invpack& out) {
-  const int64_t n_pad = (n + 15) / 16 * 16, T = n_pad / 16;
-  const int RB = (int)((T + 3) / 4);
+  const int64_t n_pad = (n + 15) / 16 * 16;
+  const int RB = cf_inv_rowblocks(n);
   out.n = n;
   out.n_pad = n_pad;
   out.n_rowblocks = RB;

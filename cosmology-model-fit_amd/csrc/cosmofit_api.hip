@@ -1201,6 +1201,7 @@ extern "C" int cf_get_info(cf_handle* h, cf_info* info) {
 // Which form of the per-walker kernel cf_eval / cf_eval_device run for a batch of W walkers: 0 the workgroup form
 // (walker_fast_kernel), 1 the streaming form (walker_stream_kernel), 2 the generic kernel (or a likelihood with a kernel of its own).
 static bool small_frag_b(const cf_handle* h, int64_t Wc);
+static bool small_frag_wanted(const cf_handle* h, int64_t Wc);
 static int sn_parts_for(const cf_dev_desc& d, int64_t Wc);
 static bool walker_stream_chosen(const cf_handle* h, int64_t Wc, bool frag_b, int sn_parts);
 extern "C" int cf_walker_form(cf_handle* h, int64_t W) {
@@ -1208,6 +1209,13 @@ extern "C" int cf_walker_form(cf_handle* h, int64_t W) {
   std::lock_guard<std::mutex> lk(h->mu);
   if (h->qsr || !walker_fast_ok(h->d)) return 2;
   return walker_stream_chosen(h, W, small_frag_b(h, W), sn_parts_for(h->d, W)) ? 1 : 0;
+}
+// Does the per-walker stage hand a batch of W walkers' residuals to the small-batch solve kernel in its fragment order (1), or in
+// walker rows (0: the generic per-walker kernel, CF_TUNE small_frag=0, every batch of the throughput solve kernel)?
+extern "C" int cf_solve_frag_order(cf_handle* h, int64_t W) {
+  if (!h || W < 1) return fail(CF_ERR_INVALID, "cf_solve_frag_order: null handle or W < 1");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return small_frag_wanted(h, W) ? 1 : 0;
 }
 
 extern "C" int cf_enable_timing(cf_handle* h, int slots) {
@@ -1311,9 +1319,14 @@ struct TriGemmArgs {
   bool frag_b;  // `delta` holds the panels' residuals in the small-batch kernel's fragment order (walker_fast_kernel, frag_b)
 };
 
-template <int NP, int PF>
-static int launch_tri_gemm_t(const TriGemmArgs& a, hipStream_t st) {
-  const int panels = (int)((a.W + 16 * NP - 1) / (16 * NP));
+// The grid of the throughput solve kernel for W walkers in panels of 16 np: what launch_tri_gemm_t launches and cf_solve_form reports.
+struct GemmGrid {
+  int panels, ppg, n_groups, split_levels, n_wgs, snake;
+};
+static GemmGrid tri_gemm_grid(int np, int n_rb, int64_t W) {
+  GemmGrid g;
+  g.panels = (int)((W + 16 * np - 1) / (16 * np));
+  const int panels = g.panels;
   // Panel groups: the grid runs group by group (a group = `ppg` panels x all row blocks), so that a group's residual rows
   // stay in the 256 MB Infinity Cache while its 27 row blocks pass over them.  Up to 8192 walkers (256 panels of 32: 113 MB
   // of residual rows) one group is best (W = 4096: one group 226 us, two 229 us, four 249 us -- the factor streams are
@@ -1323,34 +1336,43 @@ static int launch_tri_gemm_t(const TriGemmArgs& a, hipStream_t st) {
   // 2.96 ms = 0.82).  CF_TUNE gemm_group=<panels> overrides (multiples of 8 so that a panel stays on one XCD; 0 = one group).
   static const int env_group = (int)cf_tune("gemm_group", -1);
   const int max_group = env_group >= 0 ? env_group : (panels > 256 ? 128 : 0);
-  int ppg = panels;
+  g.ppg = panels;
   if (max_group > 0 && panels > max_group) {
     const int n_groups = (panels + max_group - 1) / max_group;
-    ppg = ((panels + n_groups - 1) / n_groups + 7) / 8 * 8;
+    g.ppg = ((panels + n_groups - 1) / n_groups + 7) / 8 * 8;
   }
-  const int n_groups = (panels + ppg - 1) / ppg;
+  g.n_groups = (panels + g.ppg - 1) / g.ppg;
   // the lowest row blocks of a 32-walker panel as two 16-walker units each (the kernel: HALF UNITS).  Measured with the final kernel
   // over 0 / 6 / 12 levels (profiles/r04_half_units_final_kernel_raw.txt): 6 levels gain 2 % at 1024-1536 walkers (0.643 -> 0.654,
   // 0.698 -> 0.715), nothing at 640-768 and 2048, and cost 3 % at 3072 (the factor fragments feed one panel instead of two; every
   // stage of a half unit runs the guarded form).  CF_TUNE gemm_split=<levels> forces a number.
   static const int split_env = (int)cf_tune("gemm_split", -1);
-  const int split_levels = NP == 2 ? std::max(0, std::min(a.n_rb - 1, split_env >= 0 ? split_env : (panels >= 28 && panels <= 56 ? 6 : 0))) : 0;
-  const int n_wgs = n_groups * ppg * (a.n_rb + split_levels);
+  g.split_levels = np == 2 ? std::max(0, std::min(n_rb - 1, split_env >= 0 ? split_env : (panels >= 28 && panels <= 56 ? 6 : 0))) : 0;
+  g.n_wgs = g.n_groups * g.ppg * (n_rb + g.split_levels);
   // order of the row blocks inside the grid: descending; for a grid that is resident all at once, alternate blocks of 256 workgroups
   // ascending (see the kernel).  CF_TUNE gemm_order=0|1 forces one.
   static const int order_env = (int)cf_tune("gemm_order", -1);
-  const int snake = order_env >= 0 ? order_env : (n_wgs <= 1024 + 256 ? 1 : 0);  // (a few half units beyond the resident 1024 change nothing)
-  hipLaunchKernelGGL((tri_gemm_chi2_kernel<NP, PF>), dim3((unsigned)n_wgs), dim3(256), 0, st, a.epi, a.frags, a.n_ld, a.ndim, a.n_rb, a.theta,
-                     a.W, a.delta, a.w_pad, a.partial, a.arrivals, a.chi2_extra, a.out, a.out_kind, a.nonfinite, a.chi2_sn_out, ppg, snake,
-                     a.nt_last, a.diag_skip, split_levels, a.done_flag, a.done_seq);
+  g.snake = order_env >= 0 ? order_env : (g.n_wgs <= 1024 + 256 ? 1 : 0);  // (a few half units beyond the resident 1024 change nothing)
+  return g;
+}
+
+template <int NP, int PF>
+static int launch_tri_gemm_t(const TriGemmArgs& a, hipStream_t st) {
+  const GemmGrid g = tri_gemm_grid(NP, a.n_rb, a.W);
+  hipLaunchKernelGGL((tri_gemm_chi2_kernel<NP, PF>), dim3((unsigned)g.n_wgs), dim3(256), 0, st, a.epi, a.frags, a.n_ld, a.ndim, a.n_rb, a.theta,
+                     a.W, a.delta, a.w_pad, a.partial, a.arrivals, a.chi2_extra, a.out, a.out_kind, a.nonfinite, a.chi2_sn_out, g.ppg, g.snake,
+                     a.nt_last, a.diag_skip, g.split_levels, a.done_flag, a.done_seq);
   return 0;
 }
+
+// workgroups per 16-walker panel of the small-batch solve kernel: (4 / tpw) units per row block, padded to a multiple of 8
+static int tri_gemm_small_units_pad(int tpw, int n_rb) { return ((4 / tpw) * n_rb + 7) / 8 * 8; }
 
 // Small batches: one workgroup per (panel, row block, 16-row tile), see tri_gemm_small_kernel.
 template <int PF, bool FRAG, int TPW>
 static int launch_tri_gemm_small_t(const TriGemmArgs& a, hipStream_t st) {
   const int panels = (int)((a.W + 15) / 16);
-  const int units_pad = ((4 / TPW) * a.n_rb + 7) / 8 * 8;
+  const int units_pad = tri_gemm_small_units_pad(TPW, a.n_rb);
   // dynamic LDS: the last arriver's shares + row-block sums -- padded so that at most TWO workgroups fit a CU.  With several
   // panels the grid outnumbers the CUs, and left to itself the dispatcher stacks three or four of these bandwidth-bound workgroups
   // on some CUs while others hold one (75 walkers: 33.7-34.6 -> 31.8-32.2 us per call, 150 walkers with two tiles per workgroup:
@@ -1396,11 +1418,22 @@ static int tri_gemm_panel_width(int64_t W) {
   return forced == 1 ? 16 : forced == 2 ? 32 : (W > CF_NP2_FROM ? 32 : 16);
 }
 
+// tiles per workgroup of the small-batch solve kernel.  Measured: one tile per workgroup up to 96 walkers (75: 32.0 against 34.0 us),
+// two beyond (128: 37 against 38.5).  CF_TUNE small_tpw=1|2 forces one.
+static int tri_gemm_small_tpw(int64_t W) {
+  static const int tpw_env = (int)cf_tune("small_tpw", 0);
+  return (tpw_env == 1 || tpw_env == 2) ? tpw_env : (W <= 96 ? 1 : 2);
+}
+
+// 16-row tiles of the last row block that hold rows of the factor (CF_TUNE gemm_trim=0: the padded tiles are computed too, A/B)
+static int tri_gemm_nt_last(int64_t n_pad, int n_rb) {
+  static const bool trim = cf_tune("gemm_trim", 1) != 0;
+  return trim ? (int)std::max<int64_t>(1, std::min<int64_t>(4, (n_pad - 64 * (int64_t)(n_rb - 1)) / 16)) : 4;
+}
+
 static int launch_tri_gemm(const TriGemmArgs& a, hipStream_t st) {
   if (a.W <= small_batch_max() && a.partial4) {
-    // measured: one tile per workgroup up to 96 walkers (75: 32.0 against 34.0 us), two beyond (128: 37 against 38.5)
-    static const int tpw_env = (int)cf_tune("small_tpw", 0);
-    const int tpw = (tpw_env == 1 || tpw_env == 2) ? tpw_env : (a.W <= 96 ? 1 : 2);
+    const int tpw = tri_gemm_small_tpw(a.W);
     if (tpw == 2) return a.frag_b ? launch_tri_gemm_small_t<8, true, 2>(a, st) : launch_tri_gemm_small_t<8, false, 2>(a, st);
     return a.frag_b ? launch_tri_gemm_small_t<16, true, 1>(a, st) : launch_tri_gemm_small_t<16, false, 1>(a, st);
   }
@@ -1408,13 +1441,39 @@ static int launch_tri_gemm(const TriGemmArgs& a, hipStream_t st) {
   return tri_gemm_panel_width(a.W) == 32 ? launch_tri_gemm_t<2, 2>(a, st) : launch_tri_gemm_t<1, 2>(a, st);
 }
 
+// The form launch_tri_gemm gives a batch of W walkers over a factor of n_sn rows, from the helpers it launches with (so the report
+// cannot drift from the launch): no handle, no device, a function of (n_sn, W) and the process's CF_TUNE.  Inverse-GEMM mode only.
+extern "C" int cf_solve_form(int64_t n_sn, int64_t W, int32_t out[10]) {
+  if (!out) return fail(CF_ERR_INVALID, "cf_solve_form: null output");
+  if (n_sn < 1 || n_sn > (1 << 20) || W < 1) return fail(CF_ERR_INVALID, "cf_solve_form: n_sn must be in 1..2^20 and W >= 1");
+  const int64_t n_pad = (n_sn + 15) / 16 * 16;
+  const int n_rb = cf_inv_rowblocks(n_sn);  // as cf_pack_inverse counts them for the handle
+  out[3] = n_rb;
+  out[4] = tri_gemm_nt_last(n_pad, n_rb);
+  if (W <= small_batch_max()) {
+    const int tpw = tri_gemm_small_tpw(W), panels = (int)((W + 15) / 16);
+    out[0] = 0; out[1] = 16; out[2] = tpw;
+    out[5] = 0; out[6] = 1; out[7] = panels; out[8] = 0;
+    out[9] = panels * tri_gemm_small_units_pad(tpw, n_rb);
+  } else {
+    const int pw = tri_gemm_panel_width(W);
+    const GemmGrid g = tri_gemm_grid(pw / 16, n_rb, W);
+    out[0] = 1; out[1] = pw; out[2] = 0;
+    out[5] = g.split_levels; out[6] = g.n_groups; out[7] = g.ppg; out[8] = g.snake;
+    out[9] = g.n_wgs;
+  }
+  return CF_OK;
+}
+
 // a small batch of the production path takes the fragment-ordered residuals (launch_eval)?
-static bool small_frag_b(const cf_handle* h, int64_t Wc) {
+// (small_frag_wanted: the same before the handle's first evaluation has allocated the small-batch kernel's workspace)
+static bool small_frag_wanted(const cf_handle* h, int64_t Wc) {
   static const bool frag_env = cf_tune("small_frag", 1) != 0;
   const cf_dev_desc& d = h->d;
-  const bool small_solve = d.n_sn > 0 && h->solve_mode == CF_SOLVE_INVERSE_GEMM && h->partial4.p && Wc <= small_batch_max();
+  const bool small_solve = d.n_sn > 0 && h->solve_mode == CF_SOLVE_INVERSE_GEMM && Wc <= small_batch_max();
   return frag_env && small_solve && walker_fast_ok(d) && !h->qsr;
 }
+static bool small_frag_b(const cf_handle* h, int64_t Wc) { return h->partial4.p && small_frag_wanted(h, Wc); }
 // workgroups per walker of walker_fast_kernel (CF_TUNE sn_parts=1|2|4 overrides)
 static int sn_parts_for(const cf_dev_desc& d, int64_t Wc) {
   static const int parts_env = (int)cf_tune("sn_parts", 0);
@@ -1523,8 +1582,7 @@ static int launch_eval(cf_handle* h, const double* th, int64_t Wc, double* out, 
   }
   if (ev) HIP_TRY(hipEventRecord(ev[2], st));
   if (d.n_sn > 0 && h->solve_mode == CF_SOLVE_INVERSE_GEMM) {
-    static const bool trim = cf_tune("gemm_trim", 1) != 0;  // 0: the padded tiles of the last row block are computed (A/B)
-    const int n_rb_ = h->ipack.dev.n_rowblocks, nt_last = trim ? std::max(1, std::min(4, (d.n_pad - 64 * (n_rb_ - 1)) / 16)) : 4;
+    const int n_rb_ = h->ipack.dev.n_rowblocks, nt_last = tri_gemm_nt_last(d.n_pad, n_rb_);
     static const int diag_skip = cf_tune("gemm_diag_skip", 1) != 0;  // 0: the zero tiles of the diagonal blocks are multiplied (A/B)
     TriGemmArgs a{h->epi.as<const cf_epilogue>(), h->ipack.dev.frags, d.n_ld, d.ndim, n_rb_, nt_last, diag_skip, th, Wc, delta,
                   h->max_walkers, h->partial.as<double>(), h->arrivals.as<unsigned int>(), extra, out,

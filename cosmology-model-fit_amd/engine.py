@@ -46,6 +46,18 @@ def solve_mode_of(solve="auto", latency_mode=None) -> int:
     return L.SOLVE_MODES[solve]
 
 
+SOLVE_FORM_FIELDS = ("kernel", "panel_width", "tpw", "n_rb", "nt_last", "split_levels", "n_groups", "panels_per_group", "snake",
+                     "workgroups")
+
+
+def solve_form(n_sn: int, W: int) -> dict:
+    """cf_solve_form as a dict over SOLVE_FORM_FIELDS: the form the inverse-GEMM solve gives W walkers over a factor of n_sn rows
+    under this process's CF_TUNE.  Needs no engine and no GPU."""
+    out = (C.c_int32 * 10)()
+    L.check(L.lib().cf_solve_form(int(n_sn), int(W), C.byref(out)))
+    return dict(zip(SOLVE_FORM_FIELDS, (int(v) for v in out)))
+
+
 def _default_param(name: str) -> Param:
     """A slot the caller does not name: w0 = -1, the two error-rescale factors 1, everything else unused (fixed 0)."""
     return Param(fixed=-1.0) if name == "w0" else (Param(fixed=1.0) if name in ("fcc", "fs8err") else Param())
@@ -465,6 +477,19 @@ class LikelihoodEngine:
         if rc < 0:
             L.check(rc)
         return rc
+
+    def solve_form(self, W: int) -> dict:
+        """The launch-time form of the inverse-GEMM solve for a batch of W walkers over this engine's SN block (cf_solve_form: a
+        function of n_sn, W and the process's CF_TUNE; it describes solve_mode "inverse" only): dict of kernel (0 small-batch,
+        1 throughput), panel_width, tpw, n_rb, nt_last, split_levels, n_groups, panels_per_group, snake, workgroups; plus
+        frag_order -- whether this handle's per-walker stage writes such a batch's residuals in the small-batch kernel's fragment
+        order (cf_solve_frag_order).  An unknown CF_TUNE key is silently ignored: this shows whether a key took effect."""
+        form = solve_form(self.n_sn, W)
+        rc = L.lib().cf_solve_frag_order(self._h, int(W))
+        if rc < 0:
+            L.check(rc)
+        form["frag_order"] = rc
+        return form
 
     def enable_timing(self, slots=1, stride=1):
         """Keep HIP-event timings of the last `slots` timed evaluations (0 = off); only every `stride`-th evaluation is timed."""

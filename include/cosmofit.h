@@ -399,6 +399,19 @@ int cf_last_kernel_ms(cf_handle* h, float t[2]);
  * 1 = streaming (one wave per walker, large batches; the same bits), 2 = the generic kernel.  Negative: an error code.
  * CF_TUNE walker_stream=0|1 forces the choice between 0 and 1 where both are allowed. */
 int cf_walker_form(cf_handle* h, int64_t W);
+/* The launch-time form of the inverse-GEMM solve (CF_SOLVE_INVERSE_GEMM only; the blocked solve has one form) for a batch of W
+ * walkers over an SN factor of n_sn rows: a pure function of n_sn, W and the process's CF_TUNE -- no handle, no device -- computed
+ * by the helpers the launch itself uses.  out[0] kernel (0 small-batch, 1 throughput), [1] walkers per panel (16 or 32), [2] tiles
+ * per workgroup of the small-batch kernel (1 or 2; 0 for throughput), [3] row blocks of 64 rows, [4] 16-row tiles of the last row
+ * block that hold rows of the factor (1..4; only the throughput kernel skips the others), [5] row-block levels worked as half
+ * units, [6] panel groups, [7] panels per group, [8] snake order of the row blocks (0 / 1), [9] workgroups launched.  [5]..[8]
+ * are 0, 1, the number of panels, 0 for the small-batch kernel.  An unknown CF_TUNE key is silently ignored: this is how to see
+ * that a key took effect.  n_sn in 1..2^20, W >= 1, otherwise CF_ERR_INVALID. */
+int cf_solve_form(int64_t n_sn, int64_t W, int32_t out[10]);
+/* 1: the per-walker stage writes the residuals of a batch of W walkers in the small-batch solve kernel's fragment order, 0: in
+ * walker rows (every batch of the throughput solve kernel; likelihoods that take the generic per-walker kernel; CF_TUNE
+ * small_frag=0).  A property of the handle; the result is the same bits either way.  Negative: an error code. */
+int cf_solve_frag_order(cf_handle* h, int64_t W);
 
 /* ---- stand-alone operators with the reference's signatures (host buffers) ---- */
 /* out[k] = Hermite(xq[k]; x, y, y_prime), linear extrapolation outside   interpolator.py:117-119 */

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle_np as onp
+from solve_shapes import sn_data as _sn
 from test_oracle_golden import _cmbdata, _phys
 
 pytestmark = pytest.mark.gpu
@@ -18,16 +19,6 @@ def gpu(pkg):
     if pkg.lib().cf_device_count() < 1:
         pytest.fail("GPU tests need an MI355X; no HIP device visible (there is no fallback path)")
     return pkg
-
-
-def _sn(rng, n, z_hi):
-    z = np.sort(rng.uniform(0.01, z_hi, n))
-    zh = z * (1 + 1e-3 * rng.standard_normal(n))
-    sig = rng.uniform(0.1, 0.3, n)
-    A = 0.02 * rng.standard_normal((n, min(n, 12)))
-    cov = np.diag(sig**2) + A @ A.T
-    obs = 25 + 5 * np.log10((1 + zh) * 4283.0 * z * (1 + 0.4 * z)) - 19.3 + 0.15 * rng.standard_normal(n)
-    return z, zh, obs, np.linalg.cholesky(cov)
 
 
 # CF_TEST_RANDOM_SHAPES=<n>: soak with more seeds (the default 24 keep the suite short)
