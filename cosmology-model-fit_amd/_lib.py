@@ -209,6 +209,12 @@ class cf_infl_out(C.Structure):
                 ("g", C.c_void_p), ("contrib", C.c_void_p), ("z", C.c_void_p), ("loo", C.c_void_p), ("sample", C.c_void_p)]
 
 
+CF_BRIDGE_MAX_NDIM, CF_BRIDGE_SLICE, CF_BRIDGE_RESULT_DOUBLES = 16, 2048, 8
+# cf_bridge_result of include/cosmofit.h, in index order, and cf_bridge_status
+BRIDGE_RESULT = ("log_r", "n_iter", "status", "mean_f1", "var_f1", "mean_f2", "var_f2", "r")
+CF_BRIDGE_CONVERGED, CF_BRIDGE_ITER_CAP, CF_BRIDGE_NONFINITE = range(3)
+
+
 class cf_info(C.Structure):
     _fields_ = [
         ("n_sn", C.c_int64), ("n_sn_pad", C.c_int64), ("packed_chol_bytes", C.c_int64),
@@ -319,6 +325,10 @@ EXPORTS = {
     "cf_infl_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _VP, _I64, _I32, _VP, _I32,
                                      C.POINTER(cf_infl_out), C.POINTER(cf_resid_acc), C.POINTER(cf_resid_acc)]),
     "cf_infl_set_chunk": (C.c_int, [_VP, _I64]),
+    "cf_bridge_forward": (C.c_int, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "cf_bridge_points": (C.c_int, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "cf_bridge_draw": (C.c_int, [C.c_uint64, _I64, _I64, _I32, _VP, _VP]),
+    "cf_bridge_solve": (C.c_int, [_VP, _I64, _VP, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I32, _VP, _VP, _VP]),
 }
 
 

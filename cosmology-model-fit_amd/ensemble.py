@@ -458,6 +458,27 @@ class ShardedEnsemble:
         eng = fit_report.engine_of(self.log_prob_fn, engine, "ShardedEnsemble.influence")
         return influence.chain_report(eng, self.get_chain(discard=discard, thin=thin, flat=True), **kw)
 
+    def log_evidence(self, discard: int = 0, thin: int = 1, bounds=None, engine=None, **kw):
+        """``evidence.bridge(log_prob_fn, get_chain(discard, thin), lo, hi, log_probs=get_log_prob(discard, thin), **kw)``: ln Z
+        with its error from the stored chain by bridge sampling (an ``evidence.BridgeResult``), where the reference's scripts
+        call ``log_evidence(samples, log_probs, log_probability, bounds)``.  bounds: the box [ndim, 2] the sampler's callable
+        returns -inf outside of (default: the ``bounds`` of the engine behind ``engine.torch_log_prob()``, or of engine=).
+        Keywords: method, n_draws, n_eff, seed, tol, max_iter, chunk."""
+        import numpy as np
+
+        from . import evidence
+
+        if bounds is None:
+            bounds = getattr(engine if engine is not None else getattr(self.log_prob_fn, "engine", None), "bounds", None)
+            if bounds is None:
+                raise ValueError("ShardedEnsemble.log_evidence needs the box: pass bounds= [ndim, 2], or sample with "
+                                 "engine.torch_log_prob() of an engine that has bounds")
+        b = np.asarray(bounds, dtype=np.float64)
+        if b.shape != (self.ndim, 2):
+            raise ValueError(f"bounds must be [{self.ndim}, 2]: (lo, hi) per parameter")
+        return evidence.bridge(self.log_prob_fn, self.get_chain(discard=discard, thin=thin), b[:, 0], b[:, 1],
+                               log_probs=self.get_log_prob(discard=discard, thin=thin), **kw)
+
     def mean_path(self, discard: int = 0) -> torch.Tensor:
         """The walker mean per stored step, [n, ndim] on the device: the black line of the reference's trace plot
         (corner_plot.py:30)."""
