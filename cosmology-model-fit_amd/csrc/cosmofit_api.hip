@@ -1218,6 +1218,31 @@ extern "C" int cf_solve_frag_order(cf_handle* h, int64_t W) {
   return small_frag_wanted(h, W) ? 1 : 0;
 }
 
+// The launch form of small_blocks_kernel for a batch of Wc walkers: what launch_eval launches and cf_small_blocks_form reports.
+// Sixteen lanes per walker, sixteen walkers per workgroup (4096 walkers = one wave per SIMD, issue-bound); below that the chip is
+// not full and the time is the serial chain of a lane: a whole wave per walker then (4 instead of 13 Gauss-Legendre nodes per
+// lane).  Measured on the w0waCDM joint likelihood: 16 walkers 50.7 -> 45.1 us per call, 256: 77 -> 67, 2048: 193 -> 185,
+// 4096: 329 -> 334 (profiles/r03_small_blocks_lanes_ab.txt).  The sums do not depend on the width (VirtualLaneSum): a walker's
+// result is the same bits either way (tests/test_gpu_blocks_shapes.py).  CF_TUNE sb_wide_max=<walkers> moves the switch.
+// ... and TWO waves per walker: the BAO / cosmic-chronometer blocks beside the powers and the CMB integrals (small_blocks_kernel,
+// ROLES): 16 walkers 44.6 -> 37.9 us per call, 256: 67 -> 60, 2048: 184 -> 182.  CF_TUNE sb_roles_max=<walkers> (0 = never).
+static void small_blocks_form_of(int64_t Wc, int* lanes, int* roles) {
+  static const int64_t wide_max = cf_tune("sb_wide_max", 2048);
+  static const int64_t roles_max = cf_tune("sb_roles_max", 2048);
+  *lanes = Wc <= wide_max ? 64 : 16;
+  *roles = (*lanes == 64 && Wc <= roles_max) ? 2 : 1;
+}
+// lanes + 256 * roles of the small-blocks launch for a batch of W walkers (272: 16 x 1, 320: 64 x 1, 576: 64 x 2), 0 for a handle
+// without small blocks (no BAO, compressed-CMB or cosmic-chronometer block, or a quasar handle, whose kernel evaluates its own BAO).
+extern "C" int cf_small_blocks_form(cf_handle* h, int64_t W) {
+  if (!h || W < 1) return fail(CF_ERR_INVALID, "cf_small_blocks_form: null handle or W < 1");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->qsr || !h->has_small_blocks) return 0;
+  int lanes, roles;
+  small_blocks_form_of(W, &lanes, &roles);
+  return lanes + 256 * roles;
+}
+
 extern "C" int cf_enable_timing(cf_handle* h, int slots) {
   if (!h) return fail(CF_ERR_INVALID, "cf_enable_timing: null handle");
   if (slots < 0 || slots > 4096) return fail(CF_ERR_INVALID, "cf_enable_timing: slots must be in 0..4096");
@@ -1562,16 +1587,9 @@ static int launch_eval(cf_handle* h, const double* th, int64_t Wc, double* out, 
                          bao_nodes, (d2*)nullptr);
     if (ev) HIP_TRY(hipEventRecord(ev[1], st));  // between walker_kernel and the small-block / growth kernels
     if (h->has_small_blocks) {
-      // sixteen lanes per walker, sixteen walkers per workgroup (4096 walkers = one wave per SIMD, issue-bound); below that the
-      // chip is not full and the time is the serial chain of a lane: a whole wave per walker then (4 instead of 13 Gauss-Legendre
-      // nodes per lane).  Measured on the w0waCDM joint likelihood: 16 walkers 50.7 -> 45.1 us per call, 256: 77 -> 67, 2048: 193 ->
-      // 185, 4096: 329 -> 334 (profiles/r03_small_blocks_lanes_ab.txt).  The sums do not depend on the width (VirtualLaneSum): a
-      // walker's result is the same bits either way.  CF_TUNE sb_wide_max=<walkers> moves the switch.
-      static const int64_t wide_max = cf_tune("sb_wide_max", 2048);
-      // ... and TWO waves per walker: the BAO / cosmic-chronometer blocks beside the powers and the CMB integrals (small_blocks_kernel,
-      // ROLES): 16 walkers 44.6 -> 37.9 us per call, 256: 67 -> 60, 2048: 184 -> 182.  CF_TUNE sb_roles_max=<walkers> (0 = never).
-      static const int64_t roles_max = cf_tune("sb_roles_max", 2048);
-      const int lanes = Wc <= wide_max ? 64 : 16, roles = (lanes == 64 && Wc <= roles_max) ? 2 : 1, per_wg = 256 / (lanes * roles);
+      int lanes, roles;  // 16 x 1 for large batches, 64 x 1 or 64 x 2 below (small_blocks_form_of)
+      small_blocks_form_of(Wc, &lanes, &roles);
+      const int per_wg = 256 / (lanes * roles);
       hipLaunchKernelGGL(pick_small_blocks(d.ez_model, d.fde, lanes, roles), dim3((unsigned)((Wc + per_wg - 1) / per_wg)), dim3(256), 0, st, d, th, Wc,
                          (const d2*)bao_nodes, extra, blocks_out, bao_out);
     }

@@ -224,7 +224,8 @@ __device__ __forceinline__ double rsqrt_pos(double x) {
 // sqrt and quotient for positive, finite, normal operands whose results are normal too (densities, 1 + z, E^2 at the Gauss-Legendre
 // nodes of the CMB distances): the library routines' own sequences -- v_rsq + one Goldschmidt step + two corrections; v_rcp + two
 // Newton steps + the residual step of v_div_fmas -- without their exponent scaling and class selects, which is what such operands
-// never take: the SAME BITS as sqrt() and a / b there, 10 instead of 19 and 8 instead of 12 instructions.
+// never take: the SAME BITS as sqrt() and a / b there, 10 instead of 19 and 8 instead of 12 instructions.  The quotient's numerator
+// may also be negative or a zero of either sign (the CPL exponent -3 wa z / (1 + z)); the denominator is positive.
 __device__ __forceinline__ double sqrt_pos(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;
@@ -239,7 +240,10 @@ __device__ __forceinline__ double div_pos(double a, double b) {
   r = fma(fma(-b, r, 1.0), r, r);
   r = fma(fma(-b, r, 1.0), r, r);
   const double q = a * r;
-  return fma(fma(-b, q, a), r, q);
+  // the residual a - b q with its sign turned twice: the same bits for every non-zero numerator (of either sign), and a zero
+  // numerator keeps its sign as in a / b -- the CPL exponent at the Gauss-Legendre nodes hands over -3 wa z = -0.0 where wa = 0
+  // (fma(-b, q, a) is +0 for a = q = -0, and the quotient came out +0; tests/test_gpu_parity.py)
+  return fma(-fma(b, q, -a), r, q);
 }
 
 // Grid node i of np.linspace(0, z_max, G): i*step, last node forced to z_max (sn/pantheon.py:16).
@@ -1260,7 +1264,7 @@ __device__ __forceinline__ double group_quadratic_form(const double* __restrict_
 // z* / r_drag powers, then the compressed-CMB integrals; wave B the cosmic chronometers and the BAO numerators (table look-ups, the
 // cube root), which need nothing from A but the final division by r_d.  Two workgroup barriers: after the first B reads r_d from LDS
 // and finishes the BAO block while A integrates, after the second A adds B's two chi^2 and writes the walker's results.  Every
-// operation and every order of operations is that of the one-role form: the same bits (tests/test_gpu_joint.py, test_gpu_random_shapes.py).
+// operation and every order of operations is that of the one-role form: the same bits (tests/test_gpu_blocks_shapes.py: every form over block sizes, models and options).
 template <int MODEL, int FDE, int LANES, int ROLES>
 __global__ void __launch_bounds__(256)
 small_blocks_kernel(cf_dev_desc d, const double* __restrict__ theta, int64_t W, const d2* __restrict__ bao_nodes,

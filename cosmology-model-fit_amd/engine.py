@@ -478,6 +478,16 @@ class LikelihoodEngine:
             L.check(rc)
         return rc
 
+    def small_blocks_form(self, W: int):
+        """(lanes per walker, waves per walker) of the small-blocks kernel (z* / r_drag, compressed CMB, cosmic chronometers,
+        BAO) for a batch of W walkers: (16, 1) above CF_TUNE sb_wide_max (default 2048 walkers), (64, 2) up to sb_roles_max
+        (default 2048), (64, 1) between the two; the same bits in all three.  None for an engine without such a block.  An unknown
+        CF_TUNE key is silently ignored: this shows whether a key took effect (cf_small_blocks_form)."""
+        rc = L.lib().cf_small_blocks_form(self._h, int(W))
+        if rc < 0:
+            L.check(rc)
+        return (rc % 256, rc // 256) if rc else None
+
     def solve_form(self, W: int) -> dict:
         """The launch-time form of the inverse-GEMM solve for a batch of W walkers over this engine's SN block (cf_solve_form: a
         function of n_sn, W and the process's CF_TUNE; it describes solve_mode "inverse" only): dict of kernel (0 small-batch,

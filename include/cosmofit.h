@@ -412,6 +412,11 @@ int cf_solve_form(int64_t n_sn, int64_t W, int32_t out[10]);
  * walker rows (every batch of the throughput solve kernel; likelihoods that take the generic per-walker kernel; CF_TUNE
  * small_frag=0).  A property of the handle; the result is the same bits either way.  Negative: an error code. */
 int cf_solve_frag_order(cf_handle* h, int64_t W);
+/* The launch form of the small-blocks kernel (z* / r_drag fits, compressed CMB, cosmic chronometers, BAO) for a batch of W
+ * walkers under the process's CF_TUNE: lanes per walker + 256 * waves per walker -- 272 = sixteen lanes (W > sb_wide_max, default
+ * 2048), 320 = one wave (only with sb_roles_max below W), 576 = two waves (the default up to 2048 walkers); the same bits in all
+ * three.  0: the handle has none of these blocks (or is a quasar handle).  Negative: an error code (null handle, W < 1). */
+int cf_small_blocks_form(cf_handle* h, int64_t W);
 
 /* ---- stand-alone operators with the reference's signatures (host buffers) ---- */
 /* out[k] = Hermite(xq[k]; x, y, y_prime), linear extrapolation outside   interpolator.py:117-119 */

@@ -472,6 +472,29 @@ def test_positive_operand_sqrt_and_quotient_are_the_library_bits(gpu):
     assert np.array_equal(out[:, 1], np.sqrt(a)) and np.array_equal(out[:, 3], a / b)
 
 
+def test_quotient_of_a_negative_or_zero_numerator_is_the_library_bits(gpu):
+    """div_pos with the numerators the CPL exponent at the Gauss-Legendre nodes hands it (H_at_gl_node: -3 wa z over 1 + z): negative
+    for wa > 0, -0.0 for wa = 0 -- and +0.0 -- over positive denominators.  Only the two quotient columns are compared (the square
+    root of such operands is not claimed): the same bits as a / b, the sign of a zero included."""
+    import ctypes as C
+    rng = np.random.default_rng(6)
+    b = np.concatenate([1.0 + np.exp(rng.uniform(np.log(1e-6), np.log(1e8), 200000)), rng.uniform(0.5, 4.0, 50000),
+                        np.exp(rng.uniform(-230, 230, 50000)), [1.0, 3.0, 7.0, 0.1, 1e-100, 1e100, 1100.0, 2.5]])
+    a = -np.concatenate([3 * rng.uniform(0.0, 2.0, 200000) * (b[:200000] - 1.0), rng.uniform(0.5, 4.0, 50000),
+                         np.exp(rng.uniform(-230, 230, 50000)), [1.0, 1.0, 3.0, 1e-200, 1e-100, 1e200, 3297.0, 4.5]])
+    zeros = np.concatenate([np.full(1000, -0.0), np.full(1000, 0.0)])
+    a = np.concatenate([a, zeros])
+    b = np.concatenate([b, np.tile(b[:1000], 2)])
+    assert np.all(b > 0) and np.all(a <= 0) and np.signbit(a).sum() == a.size - 1000
+    out = np.empty((a.size, 4))
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    gpu._lib.check(gpu.lib().cf_selftest_pos_ops(p(a), p(b), a.size, p(out)))
+    bits = lambda x: np.ascontiguousarray(x).view(np.uint64)
+    bad = np.flatnonzero(bits(out[:, 2]) != bits(out[:, 3]))
+    assert bad.size == 0, f"div_pos differs from the device library's quotient at {bad.size} operands; first: {a[bad[0]]!r} / {b[bad[0]]!r} -> {out[bad[0], 2]!r} vs {out[bad[0], 3]!r}"
+    assert np.array_equal(bits(out[:, 3]), bits(a / b))
+
+
 def test_production_loop_log10_absolute_error(gpu):
     """log10_tab (table-driven, production SN loop): what a distance modulus needs is ABSOLUTE accuracy of 5 log10(d)
     at the 1e-15 level on mu ~ 25..45; bound it at 3e-16 max(1, |log10 x|) over the whole double range."""
