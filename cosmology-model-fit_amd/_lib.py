@@ -215,6 +215,17 @@ BRIDGE_RESULT = ("log_r", "n_iter", "status", "mean_f1", "var_f1", "mean_f2", "v
 CF_BRIDGE_CONVERGED, CF_BRIDGE_ITER_CAP, CF_BRIDGE_NONFINITE = range(3)
 
 
+CF_GROUP_MAX_GROUPS, CF_GROUP_MAX_M, CF_GROUP_MAX_BYTES = 1024, 1024, 256 << 20
+CF_RW_SLICE, CF_RW_MAX_NCOL, CF_RW_MAX_G, CF_RW_MEAN = 2048, 16, 4096, 8
+# cf_rw_slot of include/cosmofit.h, in slot order; the moments follow from CF_RW_MEAN on
+RW_SLOTS = ("lmax", "sum_w", "sum_w2", "max_w", "n_used", "n_skipped", "sum_w0", "sum_w0_sq")
+
+
+def rw_ncol(ncol: int) -> int:
+    """CF_RW_NCOL(ncol): doubles per column record of cf_reweight_device."""
+    return 8 + ncol + ncol * (ncol + 1) // 2
+
+
 class cf_info(C.Structure):
     _fields_ = [
         ("n_sn", C.c_int64), ("n_sn_pad", C.c_int64), ("packed_chol_bytes", C.c_int64),
@@ -330,6 +341,15 @@ EXPORTS = {
     "cf_bridge_points": (C.c_int, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
     "cf_bridge_draw": (C.c_int, [C.c_uint64, _I64, _I64, _I32, _VP, _VP]),
     "cf_bridge_solve": (C.c_int, [_VP, _I64, _VP, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I32, _VP, _VP, _VP]),
+    "cf_group_create": (C.c_int, [_VP, _I32, _VP, _VP, C.POINTER(_VP)]),
+    "cf_group_destroy": (None, [_VP]),
+    "cf_group_info": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "cf_group_check_args": (C.c_int, [_I64, _VP, _I32, _VP, _VP]),
+    "cf_selftest_group_host": (C.c_int, [_VP, _I64, _I64, _I64, _VP, _VP]),
+    "cf_group_quad_check_args": (C.c_int, [_I64, _I32, _VP, _I64, _I64, _VP, _I64]),
+    "cf_group_quad_device": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _VP]),
+    "cf_reweight_check_args": (C.c_int, [_VP, _I64, _I64, _I32, _VP, _I64, _I32, _VP, _VP]),
+    "cf_reweight_device": (C.c_int, [_VP, _I64, _I64, _I32, _VP, _VP, _I64, _I32, _VP, _VP, _VP]),
 }
 
 

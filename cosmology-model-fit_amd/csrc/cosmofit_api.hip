@@ -25,6 +25,7 @@
 #include "cf_pack.h"
 #include "cf_stream_pack.h"
 #include "cosmofit_device.h"
+#include "cosmofit_group.h"
 #include "cosmofit_infl.h"
 #include "cosmofit_mock.h"
 #include "cosmofit_resid.h"
@@ -3017,6 +3018,13 @@ extern "C" void cf_prec_destroy(cf_prec* p) {
 extern "C" int cf_prec_diag(cf_prec* p, double* out_n) {
   if (!p || !out_n) return fail(CF_ERR_INVALID, "cf_prec_diag: null argument");
   memcpy(out_n, p->kdiag_host.data(), p->kdiag_host.size() * 8);
+  return CF_OK;
+}
+
+// what cosmofit_group.hip reads of a cf_prec (cosmofit_group.h)
+int cf_prec_look(const cf_prec* p, cf_prec_view* out) {
+  if (!p || !out) return fail(CF_ERR_INVALID, "cf_group: null cf_prec");
+  *out = cf_prec_view{p->n, p->kp, p->device, p->K.as<const double>(), p->kdiag_host.data()};
   return CF_OK;
 }
 

@@ -1,0 +1,656 @@
+// cosmofit_group.hip — leave-group-out fits: the chi^2 a group of data carries given all the others, for every chain sample, and
+// the importance summary that turns it into the posterior without the group (include/cosmofit.h: cf_group_*, cf_reweight_device;
+// the driver is cosmology-model-fit_amd/leaveout.py).
+//
+// With K = C^-1, g = K r (cf_prec_apply_device / cf_infl_device) and a group B of m data,
+//   q_B = g_B^T (K_BB)^-1 g_B >= 0,      chi^2 of the data without B = chi^2 - q_B      (no refit of the covariance)
+// q_B is the chi^2 of the leave-group-out residual e_B = K_BB^-1 g_B, whose covariance is K_BB^-1.  The group object holds,
+// per group, X_B = L_B^-1 of K_BB = L_B L_B^T: factored and inverted on the host in `long double` with compensated sums (as
+// cf_prec_create does its substitution), rounded once, stored lower triangular row-major at pitch mp = m rounded up to 16 with
+// zeros in the padding and above the diagonal.  Then y = X_B g_B and q_B = sum_j y_j^2.
+//
+// group_quad_kernel: q[S, G] from g[S, n] on FP64 matrix cores (v_mfma_f64_16x16x4_f64; operand maps as prec_gemm_kernel of
+// cosmofit_infl.hip: lane l holds A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15], result register r of the lane is
+// D[(l>>4) + 4 r][l&15]; here A = the gathered rows of g and B[k][j] = X_B[j][k]).  A workgroup of four waves owns 64 rows of ONE
+// group, wave w its rows 16 w .. 16 w + 15 across a block of 64 columns of y (four 16 x 16 tiles), so that every y_j of a row, and
+// then the whole sum of squares of the row, lives in one wave.  The columns of y are walked in blocks of 64; for each block the k
+// range 0 .. block end is walked in tiles of 32 staged through LDS (the group's columns of g gathered through the index list, and
+// the rows of X_B; both at pitch 34 doubles: the fragment reads of a half wave fall on 32 different 8-byte banks), the next
+// tile's global loads issued before the current tile's MFMAs.  The 16 x 16 x 4 steps above the diagonal of X_B are skipped.
+//
+// Order of summation, fixed by m alone: every y_j has ONE accumulator and its k loop is ascending in steps of 4 over
+// 0 .. 16 (j / 16 + 1); lane c of the row's sixteen then adds y_j^2 for j = c, c + 16, c + 32, ... ascending with one fused
+// multiply-add each to a partial that starts at 0.0, and the sixteen partials are combined by the fixed xor butterfly (8, 4, 2, 1).
+// So the bits of q[s, b] depend on row s of g and on group b only: not on S, the row's position, which other groups the object
+// holds, the launch geometry or the stream.  Rows >= S and columns the group does not hold are never read.  A non-finite entry
+// of g_B is replaced by 0.0 where it is loaded and its row flagged; a flagged row's q is NaN for this group (a select, not
+// 0 x NaN in the padding).  q is a sum of squares from +0.0: q >= 0, and a zero row gives +0.0.  No atomics, plain vector stores.
+//
+// cf_reweight_device: the importance summary of any log-weights lw[S, G] over columns x[S, ncol] (cosmofit.h has the record).
+// Phase one is the exact maximum of the used rows of positive base weight per column (no order matters).  Phase two sums in cf_kde_sum_device's order:
+// slices of CF_RW_SLICE consecutive rows, the terms of a slice added one by one in ascending row to a partial that starts at
+// 0.0 (one thread per statistic of a column walks the slice; the weights of a tile of 256 rows are formed once, one exp per row
+// and column, and staged through LDS for four columns at a time), the partials of the slices stored with plain vector stores
+// and added in ascending slice order by rw_combine_kernel.  One launch form; the bits of a column's record depend on that column of lw, on w0, x and the pivot only.
+// The only exponential is of lw - lmax <= 0.  No float atomics.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/cosmofit.h"
+#include "cosmofit_group.h"
+
+extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------------------------------------
+// group_quad_kernel
+// ------------------------------------------------------------------------------------------------
+#define GQ_TPB 256
+#define GQ_BM 64           // rows of g per workgroup, 16 per wave
+#define GQ_BN 64           // columns of y per pass
+#define GQ_BK 32           // k tile staged through LDS
+#define GQ_P (GQ_BK + 2)   // LDS pitch of a staged row of g_B and of X_B
+
+struct cf_group_dev {
+  const int64_t* i_off;  // [G + 1] where a group's indices begin in idx
+  const int64_t* x_off;  // [G] where a group's X_B begins in X (doubles)
+  const int32_t* idx;
+  const double* X;
+};
+
+__global__ void __launch_bounds__(GQ_TPB) group_quad_kernel(cf_group_dev gd, const double* __restrict__ g, int64_t g_pitch, int64_t S,
+                                                            double* __restrict__ q, int64_t q_pitch) {
+  __shared__ double Gs[GQ_BM * GQ_P];
+  __shared__ double Xs[GQ_BN * GQ_P];
+  __shared__ int bad[GQ_BM];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y;
+  const int64_t row0 = (int64_t)blockIdx.x * GQ_BM;
+  const int64_t i0 = gd.i_off[b];
+  const int m = (int)(gd.i_off[b + 1] - i0), mp = (m + 15) & ~15;
+  const int32_t* __restrict__ idx = gd.idx + i0;
+  const double* __restrict__ X = gd.X + gd.x_off[b];
+  // staging: thread t fetches g[row0 + (t>>5) + 8 j][idx[k0 + (t&31)]] and X_B[j0 + (t>>5) + 8 j][k0 + (t&31)], j < 8
+  const int fk = tid & 31, fr = tid >> 5;
+  double greg[8], xreg[8];
+  unsigned nonfinite = 0;  // bit j: a non-finite entry met in row fr + 8 j
+  auto fetch = [&](int j0, int k0) {
+    const int k = k0 + fk;
+    const bool held = k < m;
+    const int col = held ? idx[k] : 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int64_t row = row0 + fr + 8 * j;
+      const double v = (row < S && held) ? g[row * g_pitch + col] : 0.0;
+      const bool fin = isfinite(v);
+      nonfinite |= fin ? 0u : (1u << j);
+      greg[j] = fin ? v : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int jr = j0 + fr + 8 * j;
+      xreg[j] = (jr < mp && k < mp) ? X[(int64_t)jr * mp + k] : 0.0;
+    }
+  };
+  if (tid < GQ_BM) bad[tid] = 0;
+  __syncthreads();
+  const double* a_lds = Gs + (16 * wave + (lane & 15)) * GQ_P + (lane >> 4);
+  const double* b_lds = Xs + (lane & 15) * GQ_P + (lane >> 4);
+  double part[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int j0 = 0; j0 < mp; j0 += GQ_BN) {
+    d4 acc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = d4{0.0, 0.0, 0.0, 0.0};
+    const int k_end = min(mp, j0 + GQ_BN);  // a multiple of 16
+    const int n_tiles = (k_end + GQ_BK - 1) / GQ_BK;
+    fetch(j0, 0);
+    for (int tile = 0; tile < n_tiles; ++tile) {
+      const int k0 = tile * GQ_BK;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        Gs[(fr + 8 * j) * GQ_P + fk] = greg[j];
+        Xs[(fr + 8 * j) * GQ_P + fk] = xreg[j];
+        if ((nonfinite >> j) & 1u) bad[fr + 8 * j] = 1;
+      }
+      __syncthreads();
+      if (tile + 1 < n_tiles) fetch(j0, k0 + GQ_BK);
+      if (k0 + GQ_BK <= j0) {  // wholly below the diagonal: every step of all four tiles (wave-uniform, as all conditions here)
+#pragma unroll 2
+        for (int kk = 0; kk < GQ_BK; kk += 4) {
+          const double a = a_lds[kk];
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b_lds[16 * u * GQ_P + kk], acc[u], 0, 0, 0);
+        }
+      } else {  // the two k tiles that cross the diagonal: tile u takes the steps k < j0 + 16 u + 16 while it lies inside mp
+#pragma unroll 1
+        for (int kk = 0; kk < GQ_BK; kk += 4) {
+          const int k = k0 + kk;
+          if (k >= k_end) break;
+          const double a = a_lds[kk];
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (j0 + 16 * u < mp && k < j0 + 16 * u + 16)
+              acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b_lds[16 * u * GQ_P + kk], acc[u], 0, 0, 0);
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) part[r] = fma(acc[u][r], acc[u][r], part[r]);
+  }
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double v = part[r];
+#pragma unroll
+    for (int msk = 8; msk >= 1; msk >>= 1) v += __shfl_xor(v, msk);
+    const int lr = 16 * wave + (lane >> 4) + 4 * r;
+    const int64_t row = row0 + lr;
+    if ((lane & 15) == 0 && row < S) q[row * q_pitch + b] = bad[lr] ? nan : v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The group object: host half
+// ------------------------------------------------------------------------------------------------
+#define CF_GROUP_MAX_N 32768
+
+// s + c carries the running sum (Knuth's TwoSum, branch-free), as prec_add of cosmofit_api.hip
+static inline void grp_add(long double& s, long double& c, long double p) {
+  const long double t = s + p, z = t - s;
+  c += (s - (t - z)) + (p - z);
+  s = t;
+}
+
+// K_BB = L L^T then X = L^-1, both in long double with compensated sums; X [m * m] row-major rounded once (zeros above the
+// diagonal).  at(a, b), a >= b, is K_BB[a][b].  Returns the column of the first non-positive pivot, or -1.
+template <class At>
+static int grp_inverse_factor(int m, At at, double* X, int64_t pitch) {
+  std::vector<long double> L((size_t)m * m, 0.0L), Xc((size_t)m * m, 0.0L);  // L row-major, Xc column-major
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j <= i; ++j) {
+      long double s = (long double)at(i, j), c = 0.0L;
+      const long double *li = &L[(size_t)i * m], *lj = &L[(size_t)j * m];
+      for (int k = 0; k < j; ++k) grp_add(s, c, -(li[k] * lj[k]));
+      const long double v = s + c;
+      if (j == i) {
+        if (!(v > 0.0L) || !std::isfinite((double)v)) return j;
+        L[(size_t)i * m + i] = sqrtl(v);
+      } else {
+        L[(size_t)i * m + j] = v / lj[j];
+      }
+    }
+  for (int j = 0; j < m; ++j) {
+    long double* xj = &Xc[(size_t)j * m];
+    xj[j] = 1.0L / L[(size_t)j * m + j];
+    for (int i = j + 1; i < m; ++i) {
+      const long double* li = &L[(size_t)i * m];
+      long double s = 0.0L, c = 0.0L;
+      for (int k = j; k < i; ++k) grp_add(s, c, li[k] * xj[k]);
+      xj[i] = -(s + c) / li[i];
+    }
+  }
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j <= i; ++j) X[(size_t)i * pitch + j] = (double)Xc[(size_t)j * m + i];
+  return -1;
+}
+
+static std::string grp_name(int32_t b) { return "group " + std::to_string(b); }
+
+static int grp_check(const std::string& F, int64_t n, const double* kdiag, int32_t n_groups, const int64_t* offsets,
+                     const int32_t* idx) {
+  if (n < 1 || n > CF_GROUP_MAX_N) return cf_set_error(CF_ERR_INVALID, F + "n must be in 1..32768");
+  if (n_groups < 1 || n_groups > CF_GROUP_MAX_GROUPS) return cf_set_error(CF_ERR_INVALID, F + "n_groups must be in 1..1024");
+  if (!offsets || !idx) return cf_set_error(CF_ERR_INVALID, F + "null offsets or idx");
+  if (offsets[0] != 0) return cf_set_error(CF_ERR_INVALID, F + "offsets[0] must be 0");
+  int64_t x_bytes = 0;
+  std::vector<char> seen((size_t)n);
+  for (int32_t b = 0; b < n_groups; ++b) {
+    const int64_t m = offsets[b + 1] - offsets[b];
+    if (m < 1) return cf_set_error(CF_ERR_INVALID, F + grp_name(b) + " is empty (offsets must ascend)");
+    if (m > CF_GROUP_MAX_M) return cf_set_error(CF_ERR_INVALID, F + grp_name(b) + " holds more than 1024 data");
+    const int64_t mp = (m + 15) / 16 * 16;
+    x_bytes += mp * mp * 8;
+    if (x_bytes > CF_GROUP_MAX_BYTES)
+      return cf_set_error(CF_ERR_INVALID, F + "the factors up to " + grp_name(b) + " exceed 256 MB; split the partition");
+    std::fill(seen.begin(), seen.end(), 0);
+    for (int64_t k = offsets[b]; k < offsets[b + 1]; ++k) {
+      const int32_t i = idx[k];
+      if (i < 0 || i >= n) return cf_set_error(CF_ERR_INVALID, F + grp_name(b) + " has an index outside 0..n-1");
+      if (seen[i]) return cf_set_error(CF_ERR_INVALID, F + grp_name(b) + " names datum " + std::to_string(i) + " twice");
+      seen[i] = 1;
+      if (kdiag && !(kdiag[i] > 0.0))
+        return cf_set_error(CF_ERR_INVALID, F + grp_name(b) + " holds datum " + std::to_string(i) +
+                                                ", which the likelihood ignores (K_ii = 0)");
+    }
+  }
+  return CF_OK;
+}
+
+extern "C" int cf_group_check_args(int64_t n, const double* kdiag, int32_t n_groups, const int64_t* offsets, const int32_t* idx) {
+  return grp_check("cf_group: ", n, kdiag, n_groups, offsets, idx);
+}
+
+extern "C" int cf_selftest_group_host(const double* K, int64_t n, int64_t ld, int64_t m, const int32_t* idx, double* X_out) {
+  const std::string F = "cf_selftest_group_host: ";
+  if (!K || !X_out) return cf_set_error(CF_ERR_INVALID, F + "null argument");
+  if (ld < n) return cf_set_error(CF_ERR_INVALID, F + "ld < n");
+  const int64_t off[2] = {0, m};
+  if (m < 1) return cf_set_error(CF_ERR_INVALID, F + "group 0 is empty (offsets must ascend)");
+  int rc = grp_check(F, n, nullptr, 1, off, idx);
+  if (rc) return rc;
+  std::fill(X_out, X_out + m * m, 0.0);
+  const int col = grp_inverse_factor((int)m, [&](int a, int b) {
+    const int64_t i = std::max(idx[a], idx[b]), j = std::min(idx[a], idx[b]);  // the lower triangle of K
+    return K[i * ld + j];
+  }, X_out, m);
+  if (col >= 0) return cf_set_error(CF_ERR_INVALID, F + "group 0: non-positive pivot at column " + std::to_string(col));
+  return CF_OK;
+}
+
+struct cf_group {
+  int64_t n = 0, n_idx = 0, x_doubles = 0;
+  int32_t n_groups = 0, max_m = 0;
+  int device = 0;
+  std::vector<int64_t> off, x_off;
+  void *d_ioff = nullptr, *d_xoff = nullptr, *d_idx = nullptr, *d_X = nullptr;
+  ~cf_group() {
+    (void)hipFree(d_ioff);
+    (void)hipFree(d_xoff);
+    (void)hipFree(d_idx);
+    (void)hipFree(d_X);
+  }
+};
+
+#define GRP_HIP(expr)                                                                                  \
+  do {                                                                                                 \
+    const hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
+  } while (0)
+
+struct GrpDevice {  // the device current while in scope
+  int prev = -1;
+  hipError_t err;
+  explicit GrpDevice(int dev) {
+    err = hipGetDevice(&prev);
+    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
+  }
+  ~GrpDevice() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+static int grp_upload(void** d, const void* h, size_t bytes) {
+  GRP_HIP(hipMalloc(d, bytes));
+  GRP_HIP(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+  return CF_OK;
+}
+
+extern "C" int cf_group_create(cf_prec* prec, int32_t n_groups, const int64_t* offsets, const int32_t* idx, cf_group** out) {
+  const std::string F = "cf_group_create: ";
+  if (!out) return cf_set_error(CF_ERR_INVALID, F + "null argument");
+  *out = nullptr;
+  cf_prec_view pv;
+  int rc = cf_prec_look(prec, &pv);
+  if (rc) return rc;
+  if ((rc = grp_check(F, pv.n, pv.kdiag_host, n_groups, offsets, idx))) return rc;
+  std::unique_ptr<cf_group> p(new cf_group());
+  p->n = pv.n;
+  p->n_groups = n_groups;
+  p->device = pv.device;
+  p->n_idx = offsets[n_groups];
+  p->off.assign(offsets, offsets + n_groups + 1);
+  p->x_off.resize((size_t)n_groups);
+  for (int32_t b = 0; b < n_groups; ++b) {
+    const int64_t m = offsets[b + 1] - offsets[b], mp = (m + 15) / 16 * 16;
+    p->x_off[b] = p->x_doubles;
+    p->x_doubles += mp * mp;
+    p->max_m = std::max<int32_t>(p->max_m, (int32_t)m);
+  }
+  GrpDevice on_device(pv.device);
+  GRP_HIP(on_device.err);
+  // K is read once: the rows the groups name, copied back synchronously
+  std::vector<int64_t> rowpos((size_t)pv.n, -1);
+  int64_t n_rows = 0;
+  for (int64_t k = 0; k < p->n_idx; ++k)
+    if (rowpos[idx[k]] < 0) rowpos[idx[k]] = n_rows++;
+  std::vector<double> Kh((size_t)n_rows * pv.n);
+  for (int64_t i = 0; i < pv.n; ++i)
+    if (rowpos[i] >= 0)
+      GRP_HIP(hipMemcpy(&Kh[(size_t)rowpos[i] * pv.n], pv.d_K + i * pv.kp, (size_t)pv.n * 8, hipMemcpyDeviceToHost));
+  std::vector<double> X((size_t)p->x_doubles, 0.0);
+  std::vector<int> bad_col((size_t)n_groups, -1);
+  unsigned nt = std::thread::hardware_concurrency();
+  nt = nt == 0 ? 1 : (nt > 16 ? 16 : nt);
+  if ((unsigned)n_groups < nt) nt = (unsigned)n_groups;
+  if (p->max_m < 64) nt = 1;
+  auto work = [&](unsigned t) {
+    for (int32_t b = (int32_t)t; b < n_groups; b += (int32_t)nt) {
+      const int32_t* gi = idx + offsets[b];
+      const int m = (int)(offsets[b + 1] - offsets[b]);
+      bad_col[b] = grp_inverse_factor(m, [&](int a, int c) {
+        const int64_t i = std::max(gi[a], gi[c]), j = std::min(gi[a], gi[c]);
+        return Kh[(size_t)rowpos[i] * pv.n + j];
+      }, X.data() + p->x_off[b], (m + 15) / 16 * 16);
+    }
+  };
+  if (nt == 1) {
+    work(0u);
+  } else {
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nt; ++t) th.emplace_back(work, t);
+    for (auto& x : th) x.join();
+  }
+  for (int32_t b = 0; b < n_groups; ++b)
+    if (bad_col[b] >= 0)
+      return cf_set_error(CF_ERR_INVALID, F + grp_name(b) + ": non-positive pivot at column " + std::to_string(bad_col[b]));
+  if ((rc = grp_upload(&p->d_ioff, p->off.data(), p->off.size() * 8))) return rc;
+  if ((rc = grp_upload(&p->d_xoff, p->x_off.data(), p->x_off.size() * 8))) return rc;
+  if ((rc = grp_upload(&p->d_idx, idx, (size_t)p->n_idx * 4))) return rc;
+  if ((rc = grp_upload(&p->d_X, X.data(), X.size() * 8))) return rc;
+  *out = p.release();
+  return CF_OK;
+}
+
+extern "C" void cf_group_destroy(cf_group* p) {
+  if (!p) return;
+  GrpDevice on_device(p->device);
+  delete p;
+}
+
+extern "C" int cf_group_info(cf_group* p, int64_t* out6, int64_t* m_out, int64_t* pitch_out) {
+  if (!p || !out6) return cf_set_error(CF_ERR_INVALID, "cf_group_info: null argument");
+  out6[0] = p->n;
+  out6[1] = p->n_groups;
+  out6[2] = p->device;
+  out6[3] = p->max_m;
+  out6[4] = p->n_idx;
+  out6[5] = p->x_doubles * 8 + p->n_idx * 4 + (int64_t)(p->off.size() + p->x_off.size()) * 8;
+  for (int32_t b = 0; b < p->n_groups; ++b) {
+    const int64_t m = p->off[b + 1] - p->off[b];
+    if (m_out) m_out[b] = m;
+    if (pitch_out) pitch_out[b] = (m + 15) / 16 * 16;
+  }
+  return CF_OK;
+}
+
+extern "C" int cf_group_quad_check_args(int64_t n, int32_t n_groups, const void* d_g, int64_t g_pitch, int64_t S, const void* d_q,
+                                        int64_t q_pitch) {
+  const std::string F = "cf_group_quad_device: ";
+  if (S < 0 || S > CF_GROUP_MAX_ROWS) return cf_set_error(CF_ERR_INVALID, F + "S out of range");
+  if (g_pitch < n) return cf_set_error(CF_ERR_INVALID, F + "g_pitch below n");
+  if (q_pitch < n_groups) return cf_set_error(CF_ERR_INVALID, F + "q_pitch below the number of groups");
+  if (S > 0 && (!d_g || !d_q)) return cf_set_error(CF_ERR_INVALID, F + "null g or q");
+  return CF_OK;
+}
+
+extern "C" int cf_group_quad_device(cf_group* p, const double* d_g, int64_t g_pitch, int64_t S, double* d_q, int64_t q_pitch,
+                                    void* hip_stream) {
+  if (!p) return cf_set_error(CF_ERR_INVALID, "cf_group_quad_device: null cf_group");
+  int rc = cf_group_quad_check_args(p->n, p->n_groups, d_g, g_pitch, S, d_q, q_pitch);
+  if (rc || S == 0) return rc;
+  GrpDevice on_device(p->device);
+  GRP_HIP(on_device.err);
+  const cf_group_dev gd{(const int64_t*)p->d_ioff, (const int64_t*)p->d_xoff, (const int32_t*)p->d_idx, (const double*)p->d_X};
+  const dim3 grid((unsigned)((S + GQ_BM - 1) / GQ_BM), (unsigned)p->n_groups);
+  hipLaunchKernelGGL(group_quad_kernel, grid, dim3(GQ_TPB), 0, (hipStream_t)hip_stream, gd, d_g, g_pitch, S, d_q, q_pitch);
+  GRP_HIP(hipGetLastError());
+  return CF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// cf_reweight_device
+// ------------------------------------------------------------------------------------------------
+#define RW_TPB 256
+#define RW_TILE 256
+#define RW_CB 4       // columns of lw per workgroup of rw_sum_kernel
+#define RW_SCALARS 7  // statistics before the moments: sum w, sum w^2, max w, n_used, n_skipped, sum w0, sum w0^2
+static_assert(CF_RW_SLICE % RW_TILE == 0, "a slice is a whole number of tiles");
+static_assert(RW_SCALARS + 1 == CF_RW_MEAN, "statistic k of a slice lands in slot k + 1 of the record");
+static_assert(RW_SCALARS + CF_RW_MAX_NCOL + CF_RW_MAX_NCOL * (CF_RW_MAX_NCOL + 1) / 2 <= RW_TPB, "one thread per statistic");
+
+struct rw_pivot {
+  double v[CF_RW_MAX_NCOL];
+};
+
+// a row counts for every column only if its x is finite and its base weight is a finite number >= 0
+__device__ __forceinline__ bool rw_row_ok(const double* __restrict__ w0, const double* __restrict__ x, int64_t x_pitch, int ncol,
+                                          int64_t s) {
+  bool ok = true;
+  for (int c = 0; c < ncol; ++c) ok = ok && isfinite(x[s * x_pitch + c]);
+  if (w0) ok = ok && isfinite(w0[s]) && w0[s] >= 0.0;
+  return ok;
+}
+
+__device__ __forceinline__ bool rw_lw_ok(double v) { return !(v != v) && v != INFINITY; }
+
+// part_max[slice * G + b] = the largest lw[s, b] of the used rows of the slice with a positive base weight (-inf when none)
+__global__ void __launch_bounds__(RW_TPB) rw_max_kernel(const double* __restrict__ lw, int64_t lw_pitch, int64_t S, int G,
+                                                        const double* __restrict__ w0, const double* __restrict__ x,
+                                                        int64_t x_pitch, int ncol, double* __restrict__ part_max) {
+  __shared__ double red[RW_TPB / 64];
+  const int tid = threadIdx.x;
+  const int64_t s0 = (int64_t)blockIdx.x * CF_RW_SLICE;
+  unsigned ok = 0;
+#pragma unroll
+  for (int i = 0; i < CF_RW_SLICE / RW_TPB; ++i) {
+    const int64_t s = s0 + tid + RW_TPB * i;
+    // a row of base weight 0 is used (and counted) but cannot set the maximum: its weight is 0 whatever its lw
+    if (s < S && rw_row_ok(w0, x, x_pitch, ncol, s) && (!w0 || w0[s] > 0.0)) ok |= 1u << i;
+  }
+  for (int b = 0; b < G; ++b) {
+    double mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < CF_RW_SLICE / RW_TPB; ++i)
+      if ((ok >> i) & 1u) {
+        const double v = lw[(s0 + tid + RW_TPB * i) * lw_pitch + b];
+        if (rw_lw_ok(v)) mx = fmax(mx, v);
+      }
+#pragma unroll
+    for (int msk = 32; msk >= 1; msk >>= 1) mx = fmax(mx, __shfl_xor(mx, msk));
+    if ((tid & 63) == 0) red[tid >> 6] = mx;
+    __syncthreads();
+    if (tid == 0) part_max[(int64_t)blockIdx.x * G + b] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(RW_TPB) rw_lmax_kernel(const double* __restrict__ part_max, int64_t n_slices, int G, int rec,
+                                                         double* __restrict__ out) {
+  const int b = blockIdx.x * RW_TPB + threadIdx.x;
+  if (b >= G) return;
+  double mx = -INFINITY;
+  for (int64_t s = 0; s < n_slices; ++s) mx = fmax(mx, part_max[s * G + b]);
+  out[(int64_t)b * rec + CF_RW_LMAX] = mx;
+}
+
+// grid (slices, ceil(G / RW_CB)): the partial sums of slice blockIdx.x for the RW_CB columns from blockIdx.y * RW_CB on,
+// part[(slice * G + b) * n_stat + k].  A tile of 256 rows is staged once for all the columns of the block (x once, one exp per row
+// and column); thread t serves statistic t % n_stat of the column slot t / n_stat, so that 256 / n_stat columns are summed side
+// by side and the rest in further passes.  Every summed statistic has the one form a = fma(A_r B_r, C_r, a) over three LDS
+// streams (1.0 where a factor is absent: x * 1.0 and fma(x, 1.0, a) = a + x are exact), so the lanes of a wave run ONE loop.
+// A (column, statistic) pair has ONE accumulator walked in ascending row, whatever the block it fell in: the order of the
+// header.  The largest weight and the two counters need no order (exact): the staging threads keep them and a tree combines them.
+#define RW_ONE 0                                     // lds[0] = 1.0
+#define RW_WT 8                                      // wt[c][r]: the weight of row r for column c of the block
+#define RW_W0 (RW_WT + RW_CB * RW_TILE)              // w0u[c][r]: the base weight where the row is used for column c, else 0.0
+#define RW_DT (RW_W0 + RW_CB * RW_TILE)              // dt[r][i] = x - pivot (0.0 in a row that is skipped for every column)
+#define RW_LDS (RW_DT + RW_TILE * CF_RW_MAX_NCOL)
+
+__device__ __forceinline__ double rw_block_reduce(double v, bool is_max, double* red, int tid) {
+#pragma unroll
+  for (int msk = 32; msk >= 1; msk >>= 1) {
+    const double o = __shfl_xor(v, msk);
+    v = is_max ? fmax(v, o) : v + o;
+  }
+  __syncthreads();
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  return is_max ? fmax(fmax(red[0], red[1]), fmax(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ void __launch_bounds__(RW_TPB) rw_sum_kernel(const double* __restrict__ lw, int64_t lw_pitch, int64_t S, int G,
+                                                        const double* __restrict__ w0, const double* __restrict__ x,
+                                                        int64_t x_pitch, int ncol, rw_pivot pivot, int rec,
+                                                        const double* __restrict__ out, double* __restrict__ part) {
+  __shared__ double lds[RW_LDS];
+  __shared__ double lmax[RW_CB], red[RW_TPB / 64];
+  const int tid = threadIdx.x, b0 = blockIdx.y * RW_CB;
+  const int nb = min(RW_CB, G - b0);
+  const int64_t s0 = (int64_t)blockIdx.x * CF_RW_SLICE;
+  if (tid < nb) lmax[tid] = out[(int64_t)(b0 + tid) * rec + CF_RW_LMAX];
+  if (tid == 0) lds[RW_ONE] = 1.0;
+  const int n_stat = RW_SCALARS + ncol + ncol * (ncol + 1) / 2;
+  const int par = min(RW_CB, RW_TPB / n_stat);  // columns summed side by side
+  const int slot = tid / n_stat, stat = tid - slot * n_stat;
+  // the three streams of this thread's statistic: offset, stride per row, and whether the offset moves with the column
+  int oa = RW_ONE, ob = RW_ONE, oc = RW_ONE, sa = 0, sb = 0, sc = 0, ca = 0, cc = 0;
+  const bool summed = slot < par && stat != 2 && stat != 3 && stat != 4;
+  if (stat == 0 || stat == 1) { oa = RW_WT; sa = 1; ca = 1; }                 // sum w, sum w^2
+  if (stat == 1) { oc = RW_WT; sc = 1; cc = 1; }
+  if (stat == 5 || stat == 6) { oa = RW_W0; sa = 1; ca = 1; }                 // sum w0, sum w0^2
+  if (stat == 6) { oc = RW_W0; sc = 1; cc = 1; }
+  if (stat >= RW_SCALARS) {
+    oa = RW_WT; sa = 1; ca = 1;
+    int ci = 0, t = stat - RW_SCALARS;
+    if (t < ncol) {                                                           // sum w d_i
+      oc = RW_DT + t; sc = ncol;
+    } else {                                                                  // sum (w d_i) d_j, i <= j
+      t -= ncol;
+      while (ci < ncol && t >= ncol - ci) {
+        t -= ncol - ci;
+        ++ci;
+      }
+      ob = RW_DT + ci; sb = ncol;
+      oc = RW_DT + ci + t; sc = ncol;
+    }
+  }
+  double acc[RW_CB], mx[RW_CB], n_used[RW_CB], n_skip[RW_CB];
+#pragma unroll
+  for (int p = 0; p < RW_CB; ++p) acc[p] = mx[p] = n_used[p] = n_skip[p] = 0.0;
+  for (int t0 = 0; t0 < CF_RW_SLICE; t0 += RW_TILE) {
+    if (s0 + t0 >= S) break;  // uniform
+    __syncthreads();          // the previous tile has been read by everyone (and lmax is there)
+    {
+      const int64_t s = s0 + t0 + tid;
+      const bool in = s < S;
+      const bool row_ok = in && rw_row_ok(w0, x, x_pitch, ncol, s);
+      const double base = (row_ok && w0) ? w0[s] : 1.0;
+#pragma unroll
+      for (int c = 0; c < RW_CB; ++c) {
+        if (c < nb) {
+          const double v = in ? lw[s * lw_pitch + b0 + c] : 0.0;
+          const bool used = row_ok && rw_lw_ok(v);
+          const bool pos = used && base > 0.0 && v > -INFINITY;  // else the weight is 0; lmax is over these rows, so v <= lmax
+          const double w = pos ? base * exp(pos ? v - lmax[c] : 0.0) : 0.0;
+          lds[RW_WT + c * RW_TILE + tid] = w;
+          lds[RW_W0 + c * RW_TILE + tid] = used ? base : 0.0;
+          mx[c] = fmax(mx[c], w);
+          n_used[c] += used ? 1.0 : 0.0;
+          n_skip[c] += (in && !used) ? 1.0 : 0.0;
+        }
+      }
+      for (int c = 0; c < ncol; ++c) lds[RW_DT + tid * ncol + c] = row_ok ? x[s * x_pitch + c] - pivot.v[c] : 0.0;
+    }
+    __syncthreads();
+    if (summed) {
+#pragma unroll
+      for (int p = 0; p < RW_CB; ++p) {
+        const int c = p * par + slot;
+        if (c >= nb) break;
+        const double* __restrict__ A = lds + oa + ca * c * RW_TILE;
+        const double* __restrict__ B = lds + ob;
+        const double* __restrict__ C = lds + oc + cc * c * RW_TILE;
+        double a = acc[p];
+#pragma unroll 8
+        for (int r = 0; r < RW_TILE; ++r) a = fma(A[r * sa] * B[r * sb], C[r * sc], a);
+        acc[p] = a;
+      }
+    }
+  }
+  // the order-free statistics of every column of the block: combined over the 256 staging threads
+#pragma unroll
+  for (int c = 0; c < RW_CB; ++c) {
+    if (c >= nb) break;  // uniform
+    const double m = rw_block_reduce(mx[c], true, red, tid);
+    const double u = rw_block_reduce(n_used[c], false, red, tid);
+    const double k = rw_block_reduce(n_skip[c], false, red, tid);
+    if (tid < 3) part[((int64_t)blockIdx.x * G + b0 + c) * n_stat + 2 + tid] = tid == 0 ? m : (tid == 1 ? u : k);
+  }
+  if (summed) {
+#pragma unroll
+    for (int p = 0; p < RW_CB; ++p) {
+      const int c = p * par + slot;
+      if (c < nb) part[((int64_t)blockIdx.x * G + b0 + c) * n_stat + stat] = acc[p];
+    }
+  }
+}
+
+// grid (G): statistic k of column b = its partials in ascending slice order from 0.0 (the largest weight: their maximum)
+__global__ void __launch_bounds__(RW_TPB) rw_combine_kernel(const double* __restrict__ part, int64_t n_slices, int G, int n_stat,
+                                                            int rec, double* __restrict__ out) {
+  const int k = threadIdx.x, b = blockIdx.x;
+  if (k >= n_stat) return;
+  double acc = 0.0;
+  for (int64_t s = 0; s < n_slices; ++s) {
+    const double v = part[(s * G + b) * n_stat + k];
+    acc = k == 2 ? fmax(acc, v) : acc + v;
+  }
+  out[(int64_t)b * rec + 1 + k] = acc;
+}
+
+extern "C" int cf_reweight_check_args(const void* d_lw, int64_t lw_pitch, int64_t S, int32_t G, const void* d_x, int64_t x_pitch,
+                                      int32_t ncol, const double* pivot, const void* d_out) {
+  const std::string F = "cf_reweight_device: ";
+  if (!d_lw || !d_x || !pivot || !d_out) return cf_set_error(CF_ERR_INVALID, F + "null argument (d_lw, d_x, pivot and d_out are needed)");
+  if (S < 1 || S > CF_RW_MAX_ROWS) return cf_set_error(CF_ERR_INVALID, F + "need 1 <= S <= 2^31");
+  if (G < 1 || G > CF_RW_MAX_G) return cf_set_error(CF_ERR_INVALID, F + "need 1 <= G <= 4096");
+  if (ncol < 1 || ncol > CF_RW_MAX_NCOL) return cf_set_error(CF_ERR_INVALID, F + "need 1 <= ncol <= 16");
+  if (lw_pitch < G) return cf_set_error(CF_ERR_INVALID, F + "lw_pitch below G");
+  if (x_pitch < ncol) return cf_set_error(CF_ERR_INVALID, F + "x_pitch below ncol");
+  for (int c = 0; c < ncol; ++c)
+    if (!std::isfinite(pivot[c])) return cf_set_error(CF_ERR_INVALID, F + "the pivot must be finite");
+  const int64_t n_slices = (S + CF_RW_SLICE - 1) / CF_RW_SLICE;
+  if (n_slices * G * (int64_t)(1 + CF_RW_NCOL(ncol)) * 8 > CF_RW_MAX_WORKSPACE)
+    return cf_set_error(CF_ERR_INVALID, F + "the partial sums of this call exceed 1 GiB; pass fewer columns of lw at a time");
+  return CF_OK;
+}
+
+extern "C" int cf_reweight_device(const double* d_lw, int64_t lw_pitch, int64_t S, int32_t G, const double* d_w0, const double* d_x,
+                                  int64_t x_pitch, int32_t ncol, const double* pivot, double* d_out, void* hip_stream) {
+  int rc = cf_reweight_check_args(d_lw, lw_pitch, S, G, d_x, x_pitch, ncol, pivot, d_out);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int64_t n_slices = (S + CF_RW_SLICE - 1) / CF_RW_SLICE;
+  const int rec = CF_RW_NCOL(ncol), n_stat = rec - 1;
+  double* work = nullptr;
+  GRP_HIP(hipMallocAsync(reinterpret_cast<void**>(&work), (size_t)(n_slices * G * (1 + n_stat)) * 8, st));
+  double* part_max = work;
+  double* part = work + n_slices * G;
+  rw_pivot pv{};
+  for (int c = 0; c < ncol; ++c) pv.v[c] = pivot[c];
+  hipLaunchKernelGGL(rw_max_kernel, dim3((unsigned)n_slices), dim3(RW_TPB), 0, st, d_lw, lw_pitch, S, (int)G, d_w0, d_x, x_pitch,
+                     (int)ncol, part_max);
+  hipLaunchKernelGGL(rw_lmax_kernel, dim3((unsigned)((G + RW_TPB - 1) / RW_TPB)), dim3(RW_TPB), 0, st, (const double*)part_max,
+                     n_slices, (int)G, rec, d_out);
+  hipLaunchKernelGGL(rw_sum_kernel, dim3((unsigned)n_slices, (unsigned)((G + RW_CB - 1) / RW_CB)), dim3(RW_TPB), 0, st, d_lw, lw_pitch, S,
+                     (int)G, d_w0, d_x,
+                     x_pitch, (int)ncol, pv, rec, (const double*)d_out, part);
+  hipLaunchKernelGGL(rw_combine_kernel, dim3((unsigned)G), dim3(RW_TPB), 0, st, (const double*)part, n_slices, (int)G, n_stat, rec,
+                     d_out);
+  hipError_t err = hipGetLastError();
+  const hipError_t freed = hipFreeAsync(work, st);  // stream-ordered: after the combine kernel
+  if (err == hipSuccess) err = freed;
+  return err == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, std::string("cf_reweight_device: ") + hipGetErrorString(err));
+}

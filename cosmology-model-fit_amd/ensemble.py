@@ -458,6 +458,18 @@ class ShardedEnsemble:
         eng = fit_report.engine_of(self.log_prob_fn, engine, "ShardedEnsemble.influence")
         return influence.chain_report(eng, self.get_chain(discard=discard, thin=thin, flat=True), **kw)
 
+    def leave_group_out(self, discard: int = 0, thin: int = 1, engine=None, **kw) -> dict:
+        """``leaveout.chain_leave_group_out(engine, get_chain(discard, thin, flat=True), **kw)``: for every group of data, the chi^2
+        it carries given the others and the posterior of the stored samples without it (reweighted on the device, with the
+        effective sample size and the Pareto tail index of the weights).  engine: as for ``fit_report``.  Keywords: groups
+        (required), block, columns, theta_ref, names."""
+        from . import fit_report, leaveout
+
+        if "weights" in kw:
+            raise TypeError("an ensemble's samples carry no weights")
+        eng = fit_report.engine_of(self.log_prob_fn, engine, "ShardedEnsemble.leave_group_out")
+        return leaveout.chain_leave_group_out(eng, self.get_chain(discard=discard, thin=thin, flat=True), **kw)
+
     def log_evidence(self, discard: int = 0, thin: int = 1, bounds=None, engine=None, **kw):
         """``evidence.bridge(log_prob_fn, get_chain(discard, thin), lo, hi, log_probs=get_log_prob(discard, thin), **kw)``: ln Z
         with its error from the stored chain by bridge sampling (an ``evidence.BridgeResult``), where the reference's scripts

@@ -403,6 +403,18 @@ class DeviceNestedSampler:
         pts, w = self._posterior_on_device()
         return influence.chain_report(eng, pts, weights=w, **kw)
 
+    def leave_group_out(self, engine=None, **kw) -> dict:
+        """``leaveout.chain_leave_group_out`` of the posterior points with their weights exp(log_w) as the base weights: per
+        group of data the chi^2 it carries given the others and the posterior without it.  engine: as for ``fit_report``.
+        Keywords: groups (required), block, columns, theta_ref, names."""
+        from . import fit_report, leaveout
+
+        if "weights" in kw:
+            raise TypeError("the nested sampler passes its own posterior weights")
+        eng = fit_report.engine_of(self.log_likelihood, engine, "DeviceNestedSampler.leave_group_out")
+        pts, w = self._posterior_on_device()
+        return leaveout.chain_leave_group_out(eng, pts, weights=w, **kw)
+
     def mean_std(self):
         """``marginals.weighted_mean_std`` of the same points and weights: (mean [ndim], std [ndim]) on the device, what the
         nautilus scripts print per parameter (getdist's ``mean`` and ``std``)."""

@@ -1189,6 +1189,74 @@ int cf_bridge_draw(uint64_t key, int64_t first, int64_t n, int32_t ndim, double*
 int cf_bridge_solve(const double* d_l1, int64_t n1, const double* d_l2, int64_t n2, double lstar, double s1, double s2, double tol,
                     int32_t max_iter, double* d_result, double* d_f2, void* hip_stream);
 
+/* ---- Leave-group-out fits (csrc/cosmofit_group.hip; the driver is cosmology-model-fit_amd/leaveout.py) ----------------------
+ * With K = C^-1, g = K r (the g rows of cf_infl_device / cf_prec_apply_device) and a group B of m data,
+ *   q_B = g_B^T (K_BB)^-1 g_B >= 0,   chi^2 of the data without B = chi^2 - q_B   (exactly; no refit of the covariance):
+ * q_B is the chi^2 of the leave-group-out residual e_B = K_BB^-1 g_B = r_B - C_BA C_AA^-1 r_A, whose covariance is K_BB^-1 (m
+ * degrees of freedom); g_i^2 / K_ii of cf_infl_device is the case m = 1.  The posterior without B is the chain reweighted by
+ * exp(+q_B / 2).
+ *
+ * cf_group: a list of groups over the n data of a cf_prec, on its device.  Group b holds idx[offsets[b] .. offsets[b + 1]):
+ * distinct indices in any order; groups may overlap.  cf_group_create reads K once (a synchronous copy back of the rows named),
+ * factors K_BB = L_B L_B^T on the host in long double with compensated sums, inverts the factor in the same precision, rounds once
+ * and uploads X_B = L_B^-1 (lower triangular, row-major, zero-padded to a pitch of m rounded up to 16) and the index lists.
+ * CF_ERR_INVALID, naming the group: n_groups outside 1 .. CF_GROUP_MAX_GROUPS, a group that is empty or holds more than
+ * CF_GROUP_MAX_M data, an index outside 0 .. n - 1 or named twice in a group, a datum with K_ii = 0 (one the likelihood ignores),
+ * all factors together beyond CF_GROUP_MAX_BYTES, a non-positive pivot (group and column).  cf_group_check_args states the
+ * argument rules without a device (kdiag [n] may be NULL: then no datum is taken as ignored).
+ * cf_group_info: out6 = {n, n_groups, device, largest m, indices held, bytes held on the device}; m_out, pitch_out [n_groups]
+ * (either may be NULL) the size and the padded pitch of every group.
+ * cf_selftest_group_host: the host half alone for one group of m data of K [n x n, row pitch ld; only the LOWER triangle is
+ * read]: X_out [m * m] row-major, zeros above the diagonal.  No device needed.
+ *
+ * cf_group_quad_device: d_q[s * q_pitch + b] = q_b of row s of d_g [S rows at pitch g_pitch >= n], for s < S and every group b,
+ * on FP64 matrix cores, asynchronous on `hip_stream`.  The bits of an element depend on its row of g and on its group only: not
+ * on S, the row's position, the other groups, or the stream.  Rows >= S and columns no group names are never read.  A non-finite
+ * g_i gives NaN in q[s, b] for exactly the groups that hold datum i.  q >= 0; a zero row gives +0.0.  CF_ERR_INVALID before
+ * anything is launched (cf_group_quad_check_args states it without a device): S outside 0 .. CF_GROUP_MAX_ROWS, g_pitch < n,
+ * q_pitch < n_groups, a null pointer with S > 0.
+ *
+ * cf_reweight_device: the importance summary of log-weights d_lw [S rows at pitch lw_pitch >= G] over the columns d_x [S rows at
+ * pitch x_pitch >= ncol] with base weights d_w0 [S] (NULL: ones).  Per column b of lw the record d_out[b * CF_RW_NCOL(ncol) + ..]
+ * (cf_rw_slot): lmax = the largest lw of the used rows whose base weight is > 0 (a row of base weight 0 has weight 0 whatever its
+ * lw: a nested run's early points, of weight exp(-40000) = 0, must not set the scale of all the others); with
+ * w = w0 exp(lw - lmax): sum w, sum w^2, the largest w, n_used, n_skipped, sum w0 and sum w0^2 over the used rows; from
+ * CF_RW_MEAN on sum w (x_i - pivot_i) [ncol], then the upper triangle of sum w (x_i - pivot_i)(x_j - pivot_j), rows i ascending,
+ * j = i .. ncol - 1.  pivot [ncol] is a HOST array (the base chain's mean keeps the second moments free of cancellation).  A row
+ * is skipped for column b, and counted, when lw[s, b] is NaN or +inf, when any x[s, :] is non-finite, or when w0[s] is not a
+ * finite number >= 0; lw = -inf is weight 0 and counts as used.  A column without a used row of positive base weight has
+ * lmax = -inf and zero sums.  Order of summation: slices of CF_RW_SLICE consecutive rows, ascending within a slice from 0.0, then
+ * the slices ascending (the cf_kde_sum_device contract); the bits of a record depend on its column of lw and on w0, x, pivot
+ * only, not on the other columns or the stream.  The only exponential is of a number <= 0.
+ * CF_ERR_INVALID before anything is launched (cf_reweight_check_args): a null pointer, S outside 1 .. CF_RW_MAX_ROWS, G outside
+ * 1 .. CF_RW_MAX_G, ncol outside 1 .. CF_RW_MAX_NCOL, a pitch below its width, a non-finite pivot, partial sums beyond
+ * CF_RW_MAX_WORKSPACE bytes. */
+#define CF_GROUP_MAX_GROUPS 1024
+#define CF_GROUP_MAX_M 1024
+#define CF_GROUP_MAX_BYTES ((int64_t)256 << 20)
+#define CF_GROUP_MAX_ROWS ((int64_t)1 << 32)
+#define CF_RW_SLICE 2048
+#define CF_RW_MAX_NCOL 16
+#define CF_RW_MAX_G 4096
+#define CF_RW_MAX_ROWS ((int64_t)1 << 31)
+#define CF_RW_MAX_WORKSPACE ((int64_t)1 << 30)
+#define CF_RW_NCOL(ncol) (8 + (ncol) + (ncol) * ((ncol) + 1) / 2)
+enum cf_rw_slot { CF_RW_LMAX = 0, CF_RW_SUM_W = 1, CF_RW_SUM_W2 = 2, CF_RW_MAX_W = 3, CF_RW_N_USED = 4, CF_RW_N_SKIPPED = 5,
+                  CF_RW_SUM_W0 = 6, CF_RW_SUM_W0_SQ = 7, CF_RW_MEAN = 8 };
+typedef struct cf_group cf_group;
+int cf_group_create(cf_prec* prec, int32_t n_groups, const int64_t* offsets, const int32_t* idx, cf_group** out);
+void cf_group_destroy(cf_group* g);
+int cf_group_info(cf_group* g, int64_t* out6, int64_t* m_out, int64_t* pitch_out);
+int cf_group_check_args(int64_t n, const double* kdiag, int32_t n_groups, const int64_t* offsets, const int32_t* idx);
+int cf_selftest_group_host(const double* K, int64_t n, int64_t ld, int64_t m, const int32_t* idx, double* X_out);
+int cf_group_quad_check_args(int64_t n, int32_t n_groups, const void* d_g, int64_t g_pitch, int64_t S, const void* d_q,
+                             int64_t q_pitch);
+int cf_group_quad_device(cf_group* g, const double* d_g, int64_t g_pitch, int64_t S, double* d_q, int64_t q_pitch, void* hip_stream);
+int cf_reweight_check_args(const void* d_lw, int64_t lw_pitch, int64_t S, int32_t G, const void* d_x, int64_t x_pitch, int32_t ncol,
+                           const double* pivot, const void* d_out);
+int cf_reweight_device(const double* d_lw, int64_t lw_pitch, int64_t S, int32_t G, const double* d_w0, const double* d_x,
+                       int64_t x_pitch, int32_t ncol, const double* pivot, double* d_out, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
