@@ -260,6 +260,7 @@ EXPORTS = {
     "cf_kernel_ms": (C.c_int, [_VP, _I64, C.POINTER(C.c_float * 2)]),
     "cf_kernel_ms3": (C.c_int, [_VP, _I64, C.POINTER(C.c_float * 3)]),
     "cf_walker_form": (C.c_int, [_VP, _I64]),
+    "cf_walker_levels": (C.c_int, [_VP, C.POINTER(C.c_int32 * 8)]),
     "cf_solve_form": (C.c_int, [_I64, _I64, C.POINTER(C.c_int32 * 10)]),
     "cf_solve_frag_order": (C.c_int, [_VP, _I64]),
     "cf_small_blocks_form": (C.c_int, [_VP, _I64]),

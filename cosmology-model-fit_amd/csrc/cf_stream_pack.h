@@ -53,4 +53,36 @@ static inline bool cf_stream_assign(const double* z_cmb, const double* step, int
   return true;
 }
 
+// The wave priority (s_setprio level, 0 .. 3) a walker's wave takes at the top of segment s: it falls 3 -> 0 as the share of the
+// walker's work already done rises, so that of the four waves of a SIMD the one that is behind outranks the one that is ahead
+// (the hardware arbitrates by priority, then age: at equal priority the oldest wave runs ahead and the four finish one after
+// another).  Cost of a segment in vector instructions, from the compiled kernel (profiles/NOTES_walker_stream.md section 2): the
+// table build, and one trip of the SN loop per 64 records.  A function of seg_off and n_seg alone.  One segment: nothing to
+// level, 0.  Segments past n_seg: 0.
+#define CF_STREAM_COST_BUILD 230
+#define CF_STREAM_COST_TRIP 60
+static inline void cf_stream_levels(const int32_t* seg_off, int n_seg, int32_t level[CF_STREAM_MAX_SEGS]) {
+  int64_t cost[CF_STREAM_MAX_SEGS], total = 0;
+  for (int s = 0; s < CF_STREAM_MAX_SEGS; ++s) {
+    level[s] = 0;
+    cost[s] = 0;
+    if (s >= n_seg) continue;
+    const int64_t n = (int64_t)seg_off[s + 1] - (int64_t)seg_off[s];
+    cost[s] = CF_STREAM_COST_BUILD + CF_STREAM_COST_TRIP * ((std::max<int64_t>(n, 0) + 63) / 64);
+    total += cost[s];
+  }
+  if (n_seg < 2) return;
+  int64_t before = 0;
+  for (int s = 0; s < n_seg && s < CF_STREAM_MAX_SEGS; ++s) {
+    level[s] = (int32_t)std::min<int64_t>(3, std::max<int64_t>(0, 3 - 4 * before / total));
+    before += cost[s];
+  }
+}
+// the table as the kernel takes it: four bits per segment
+static inline uint32_t cf_stream_levels_packed(const int32_t level[CF_STREAM_MAX_SEGS]) {
+  uint32_t p = 0;
+  for (int s = 0; s < CF_STREAM_MAX_SEGS; ++s) p |= (uint32_t)(level[s] & 3) << (4 * s);
+  return p;
+}
+
 #endif

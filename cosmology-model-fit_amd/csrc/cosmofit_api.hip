@@ -864,6 +864,11 @@ static int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** 
         h->sargs.row = h->stream_row.as<const int32_t>();
         for (int s = 0; s <= CF_STREAM_MAX_SEGS; ++s) h->sargs.seg_off[s] = plan.seg_off[s];
         h->sargs.n_seg = plan.n_seg;
+        // the wave priority per segment (cf_stream_levels); CF_TUNE walker_level=0: every wave at priority 0 throughout
+        static const bool level_on = cf_tune("walker_level", 1) != 0;
+        int32_t level[CF_STREAM_MAX_SEGS] = {};
+        if (level_on) cf_stream_levels(plan.seg_off, plan.n_seg, level);
+        h->sargs.levels = cf_stream_levels_packed(level);
         h->sargs.max_step = plan.max_step;
         h->sargs.zp1_max = plan.zp1_max;
       }
@@ -1211,6 +1216,15 @@ extern "C" int cf_walker_form(cf_handle* h, int64_t W) {
   if (h->qsr || !walker_fast_ok(h->d)) return 2;
   return walker_stream_chosen(h, W, small_frag_b(h, W), sn_parts_for(h->d, W)) ? 1 : 0;
 }
+// The wave priority the streaming form takes at the top of each of its (at most eight) segments, as in effect for this handle:
+// cf_stream_levels of the packed data, all zeros under CF_TUNE walker_level=0 and for data the streaming form does not take.
+// A batch of more than one round of the chip runs every wave at priority 0 whatever the table (walker_stream_args).
+extern "C" int cf_walker_levels(cf_handle* h, int32_t* out) {
+  if (!h || !out) return fail(CF_ERR_INVALID, "cf_walker_levels: null handle or output");
+  std::lock_guard<std::mutex> lk(h->mu);
+  for (int s = 0; s < CF_STREAM_MAX_SEGS; ++s) out[s] = h->sargs.rec ? (int32_t)((h->sargs.levels >> (4 * s)) & 3u) : 0;
+  return CF_OK;
+}
 // Does the per-walker stage hand a batch of W walkers' residuals to the small-batch solve kernel in its fragment order (1), or in
 // walker rows (0: the generic per-walker kernel, CF_TUNE small_frag=0, every batch of the throughput solve kernel)?
 extern "C" int cf_solve_frag_order(cf_handle* h, int64_t W) {
@@ -1532,14 +1546,25 @@ static bool walker_stream_ok(const cf_handle* h) {
 // So: below one round never; one round and a last round that is empty or at least a quarter full; two rounds or more always.
 // (Streaming the full rounds and giving the rest to the workgroup form in a second launch was measured too, same file: the launch
 // costs what one round gains -- 4100: 0.2416, 6144: 0.3325 -- and it was dropped.)
+static int64_t walker_stream_round(const cf_handle* h) { return (int64_t)(4 * CF_STREAM_WAVES) * (h->cu_count > 0 ? h->cu_count : 256); }
 static bool walker_stream_chosen(const cf_handle* h, int64_t Wc, bool frag_b, int sn_parts) {
   static const int mode = (int)cf_tune("walker_stream", -1);
   if (mode == 0 || frag_b || sn_parts > 1 || !walker_stream_ok(h)) return false;
   if (mode > 0) return true;
   if (!walker_stream_in_budget(h->d.ez_model, h->d.fde)) return false;
-  const int64_t round = (int64_t)(4 * CF_STREAM_WAVES) * (h->cu_count > 0 ? h->cu_count : 256);
+  const int64_t round = walker_stream_round(h);
   const int64_t full = Wc / round, rest = Wc % round;
   return full >= 2 || (full == 1 && (rest == 0 || 4 * rest >= round));
+}
+// The streaming form's arguments for a batch of Wc walkers: the wave-priority table (cf_stream_levels) goes with batches of at
+// most one round only.  Within a round it makes the four waves of a SIMD end together instead of one after another (4096 walkers:
+// the kernel 42.7 -> 38.1 us, the step 0.2216 -> 0.2190 and 0.2198 -> 0.2148 ms on two machines, profiles/NOTES_walker_level.md).
+// With a further round behind it, the waves that end early are what lets the next round's workgroups start, and levelling takes
+// that away: 5120 walkers 0.2885 -> 0.2913 ms per step, 8192 within the spread (profiles/walker_level_sweep_raw.txt).
+static cf_stream_args walker_stream_args(const cf_handle* h, int64_t Wc) {
+  cf_stream_args sa = h->sargs;
+  if (Wc > walker_stream_round(h)) sa.levels = 0;
+  return sa;
 }
 
 // One evaluation of W walkers on stream `st`: per-walker kernel (distance table, residuals; the small-blocks / growth kernels of a
@@ -1578,7 +1603,7 @@ static int launch_eval(cf_handle* h, const double* th, int64_t Wc, double* out, 
       const int sn_parts = sn_parts_for(d, Wc);
       if (walker_stream_chosen(h, Wc, frag_b, sn_parts))  // a large batch: one wave per walker, the table streamed in segments
         hipLaunchKernelGGL(pick_walker_stream(d.ez_model, d.fde), dim3((unsigned)((Wc + CF_STREAM_WAVES - 1) / CF_STREAM_WAVES)),
-                           dim3(64 * CF_STREAM_WAVES), 0, st, walker_args_of(d), h->sargs, th, Wc, delta, bao_nodes, th_copy);
+                           dim3(64 * CF_STREAM_WAVES), 0, st, walker_args_of(d), walker_stream_args(h, Wc), th, Wc, delta, bao_nodes, th_copy);
       else
         hipLaunchKernelGGL(pick_walker_fast(d.ez_model, d.fde), dim3((unsigned)(Wc * sn_parts)), dim3(512), lds, st, walker_args_of(d), th,
                            Wc, delta, bao_nodes, th_copy, frag_b ? 1 : 0, sn_parts);

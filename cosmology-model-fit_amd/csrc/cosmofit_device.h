@@ -174,6 +174,7 @@ struct cf_stream_args {
   const int32_t* row;  // [n_sn + CF_STREAM_REC_SLACK] original row of each
   int32_t seg_off[CF_STREAM_MAX_SEGS + 1];
   int32_t n_seg;
+  uint32_t levels;  // the wave priority at the top of segment s in bits 4 s .. 4 s + 3 (cf_stream_levels; 0: CF_TUNE walker_level=0)
   double max_step;  // max |step weight| (0 without a velocity step: z_cosmo = z_cmb then)
   double zp1_max;   // 1 + max z_cmb
 };

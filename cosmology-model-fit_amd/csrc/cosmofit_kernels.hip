@@ -937,7 +937,8 @@ walker_fast_kernel(cf_walker_args d, const double* __restrict__ theta, int64_t W
 // same chunk_eval, scan and carry expression, so the same bits); it keeps {cum, dh} of the segment, and the last CF_STREAM_HALO
 // nodes of the segment before, in a wave-private LDS window of 9.6 KB instead of the whole 72 KB table, and evaluates after
 // each segment the SNe packed for it at cf_create (cf_stream_pack.h).  The walker-uniform prologue runs once instead of in
-// each of eight waves; four walkers share a workgroup only for the two small reduction tables.
+// each of eight waves; four walkers share a workgroup only for the two small reduction tables.  The four waves of a SIMD start
+// together; each takes a priority that falls as its walker's work gets done (sa.levels), or they would end one after another.
 //
 // Window: node q of [halo | segment] (q = g - 512 s + 64) sits at entry q + q / 16, and the spare entry behind every 16 nodes
 // holds a copy of the node after it, so that hermite_fast's two reads stay adjacent (DistTable with chs = 4).  A lane's eight
@@ -1003,6 +1004,36 @@ __device__ __forceinline__ void sn_stream_segment(const D& d, const cf_stream_ar
   }
 }
 
+// The wave's issue priority from a wave-uniform level in a scalar register (s_setprio takes an immediate): scalar compares and
+// branches around one s_setprio, no vector instruction.  s_setprio ignores EXEC, so `level` must be provably wave-uniform.
+__device__ __forceinline__ void wave_setprio(unsigned level) {
+  switch (level) {
+    case 3: __builtin_amdgcn_s_setprio(3); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    default: __builtin_amdgcn_s_setprio(0); break;
+  }
+}
+
+#ifdef CF_DIAG_WALKER
+// DIAGNOSTIC BUILD ONLY (tools/build_variant.sh walkerdiag -DCF_DIAG_WALKER; tools/walker_timeline.py): every wave of
+// walker_stream_kernel leaves the shader clock at its first instruction, behind each segment's table build and behind its last
+// store, the real-time counter at its start and where it ran (XCC_ID, HW_ID).  The stamps go to a buffer of their own; no output
+// value depends on them.
+#define CF_WALKER_DIAG_MAX 8192
+#define CF_WALKER_DIAG_SLOTS 16  // [walker][mt first, mt behind the build of segments 0..7, mt last, XCC_ID << 32 | HW_ID, rt first, rt last]
+__device__ unsigned long long cf_walker_clock[CF_WALKER_DIAG_MAX * CF_WALKER_DIAG_SLOTS];
+extern "C" int cf_debug_walker_clock(unsigned long long* out) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(cf_walker_clock), sizeof(cf_walker_clock));
+}
+#define CF_WALKER_STAMP_V(k, v) \
+  if (lane == 0 && w < CF_WALKER_DIAG_MAX) cf_walker_clock[w * CF_WALKER_DIAG_SLOTS + (k)] = (unsigned long long)(v)
+#define CF_WALKER_STAMP(k) CF_WALKER_STAMP_V(k, __builtin_amdgcn_s_memtime())
+#else
+#define CF_WALKER_STAMP_V(k, v)
+#define CF_WALKER_STAMP(k)
+#endif
+
 template <int MODEL, int FDE>
 __global__ void __launch_bounds__(64 * CF_STREAM_WAVES, 4)
 walker_stream_kernel(cf_walker_args d, cf_stream_args sa, const double* __restrict__ theta, int64_t W, double* __restrict__ delta,
@@ -1016,6 +1047,9 @@ walker_stream_kernel(cf_walker_args d, cf_stream_args sa, const double* __restri
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t w = (int64_t)blockIdx.x * CF_STREAM_WAVES + wv;
   if (w >= W) return;
+  CF_WALKER_STAMP(0);
+  CF_WALKER_STAMP_V(11, __builtin_amdgcn_s_memrealtime());
+  CF_WALKER_STAMP_V(10, ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4));
   d2* const win = win_all[wv];
   constexpr bool POWER_LAW = FDE == CF_FDE_WCDM_D || FDE == CF_FDE_CPL_D;
   const int G = d.n_grid;
@@ -1063,6 +1097,10 @@ walker_stream_kernel(cf_walker_args d, cf_stream_args sa, const double* __restri
   wave_lds_sync();
 #pragma unroll 1
   for (int s = 0; s < sa.n_seg; ++s) {
+    // progress-keyed priority: the level falls as the walker's work gets done (cf_stream_levels), so of a SIMD's four waves the
+    // one behind outranks the one ahead and they reach the end together instead of one after another.  No wave waits for
+    // another anywhere in this kernel, so priority cannot make one depend on another.
+    wave_setprio((sa.levels >> (4 * s)) & 3u);
     const int g0 = (64 * s + lane) * 8;
     // this segment's first SN record: the load flies while the segment is built
     const unsigned sn_j = (unsigned)((fast ? sa.seg_off[s] : 0) + lane), sn_end = (unsigned)(fast ? sa.seg_off[s + 1] : d.n_sn);
@@ -1111,6 +1149,7 @@ walker_stream_kernel(cf_walker_args d, cf_stream_args sa, const double* __restri
       if (g0 + k < G) win[base + k] = (d2){loc[k] + carry, dh[k]};
     if (!(lane & 1) && g0 < G) win[base - 1] = (d2){loc[0] + carry, dh[0]};  // hermite_fast reads node i + 1 behind node i
     wave_lds_sync();
+    CF_WALKER_STAMP(1 + s);
     // node g of the window's range sits at entry g + g / 16 - (512 s - 64) * 17 / 16
     T.tab = win + (CF_STREAM_Q0 - (CF_STREAM_SEG / 16 * 17) * s);
     for (int e = lane; e < CF_BAO_NODES * d.n_aux; e += 64) {  // each BAO / growth node from the segment that built it
@@ -1135,6 +1174,8 @@ walker_stream_kernel(cf_walker_args d, cf_stream_args sa, const double* __restri
       if (lane < NH - 64) win[64 + lane] = h1;
     }
   }
+  CF_WALKER_STAMP(9);
+  CF_WALKER_STAMP_V(12, __builtin_amdgcn_s_memrealtime());
 }
 
 // H(z) at a Gauss-Legendre node of the compressed-CMB distances (small_blocks_kernel evaluates it 2 n_gl times per walker: this is

@@ -478,6 +478,16 @@ class LikelihoodEngine:
             L.check(rc)
         return rc
 
+    def walker_levels(self) -> list:
+        """The wave priority (0 .. 3) the streaming form of the per-walker kernel takes at the top of each of its at most eight
+        grid segments (cf_walker_levels): falling as a walker's work gets done, so that the waves sharing a SIMD finish together;
+        the same bits whatever the table.  All zeros under CF_TUNE walker_level=0.  The table goes with batches of at most one
+        round of the chip (16 walkers per CU); a larger batch runs at priority 0 throughout.  An unknown CF_TUNE key is silently
+        ignored: this shows whether the key took effect."""
+        out = (C.c_int32 * 8)()
+        L.check(L.lib().cf_walker_levels(self._h, C.byref(out)))
+        return list(out)
+
     def small_blocks_form(self, W: int):
         """(lanes per walker, waves per walker) of the small-blocks kernel (z* / r_drag, compressed CMB, cosmic chronometers,
         BAO) for a batch of W walkers: (16, 1) above CF_TUNE sb_wide_max (default 2048 walkers), (64, 2) up to sb_roles_max

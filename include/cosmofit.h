@@ -399,6 +399,13 @@ int cf_last_kernel_ms(cf_handle* h, float t[2]);
  * 1 = streaming (one wave per walker, large batches; the same bits), 2 = the generic kernel.  Negative: an error code.
  * CF_TUNE walker_stream=0|1 forces the choice between 0 and 1 where both are allowed. */
 int cf_walker_form(cf_handle* h, int64_t W);
+/* The wave priority (0 .. 3) the streaming form takes at the top of each of its at most eight grid segments, as in effect for
+ * this handle: it falls from 3 to 0 as the share of a walker's work already done rises (a function of the SNe per segment alone),
+ * so that the waves sharing a SIMD finish together; no result depends on it.  All zeros under CF_TUNE walker_level=0, for a grid
+ * of one segment and for data the streaming form does not take.  The table goes with batches of at most one round of the chip
+ * (16 walkers per CU: 4096 on 256 CUs); a larger batch runs every wave at priority 0.  An unknown CF_TUNE key is silently
+ * ignored: this is how to see that the key took effect. */
+int cf_walker_levels(cf_handle* h, int32_t out[8]);
 /* The launch-time form of the inverse-GEMM solve (CF_SOLVE_INVERSE_GEMM only; the blocked solve has one form) for a batch of W
  * walkers over an SN factor of n_sn rows: a pure function of n_sn, W and the process's CF_TUNE -- no handle, no device -- computed
  * by the helpers the launch itself uses.  out[0] kernel (0 small-batch, 1 throughput), [1] walkers per panel (16 or 32), [2] tiles

@@ -4,7 +4,10 @@
 // For sorted, unsorted and duplicate redshifts, 1 .. 1701 SNe and grids of 520 / 1000 / 4000 / 4096 nodes it checks that every SN
 // is evaluated exactly once, that the interval of its z_cmb (node and node + 1) lies at least HALO / 2 - 1 nodes inside the window
 // of its segment (the grid's own ends excepted: there is nothing beyond them), that the offsets are monotone and end at n_sn, and
-// that the guard admits |v| = 300 km/s (the prior box of sn/pantheon.py) for the Pantheon+ shape.
+// that the guard admits |v| = 300 km/s (the prior box of sn/pantheon.py) for the Pantheon+ shape.  For every such plan, for segment
+// populations at the edges of a trip of 64 records, for empty middle segments and for n_seg = 1 .. 8 it checks the wave-priority
+// table (cf_stream_levels): levels in 0..3, never rising, 3 for the first of several segments, 0 for a single one, a function of
+// the offsets alone.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -20,6 +23,37 @@ static int failures = 0;
       std::printf("\n");                 \
     }                                    \
   } while (0)
+
+// The wave-priority table of a plan (cf_stream_levels): levels in 0..3 that never rise with the segment, 3 for the first segment
+// of more than one, 0 for a single segment and past the last one, the packed form decodes to the table, and the table is a
+// function of seg_off[0 .. n_seg] alone (entries behind n_seg changed: the same table; recomputed here from the counts).
+static int level_tables = 0;
+static void check_levels(const int32_t* seg_off, int n_seg, const char* what) {
+  int32_t lv[CF_STREAM_MAX_SEGS];
+  cf_stream_levels(seg_off, n_seg, lv);
+  ++level_tables;
+  for (int s = 0; s < CF_STREAM_MAX_SEGS; ++s) {
+    CHECK(lv[s] >= 0 && lv[s] <= 3, "%s n_seg=%d: level[%d] = %d outside 0..3", what, n_seg, s, lv[s]);
+    CHECK(s == 0 || lv[s] <= lv[s - 1], "%s n_seg=%d: level rises at segment %d (%d -> %d)", what, n_seg, s, lv[s - 1], lv[s]);
+    CHECK(s < n_seg || lv[s] == 0, "%s n_seg=%d: level[%d] = %d behind the last segment", what, n_seg, s, lv[s]);
+  }
+  CHECK(lv[0] == (n_seg > 1 ? 3 : 0), "%s n_seg=%d: level[0] = %d", what, n_seg, lv[0]);
+  const uint32_t packed = cf_stream_levels_packed(lv);
+  for (int s = 0; s < CF_STREAM_MAX_SEGS; ++s)
+    CHECK((int32_t)((packed >> (4 * s)) & 3u) == lv[s] && ((packed >> (4 * s)) & 0xCu) == 0, "%s: packed table %08x, level[%d] = %d", what, packed, s, lv[s]);
+  // the definition, written out once more: 3 - floor(4 x share of the cost in front of s), cost = 230 + 60 x trips of 64 records
+  long long cost[CF_STREAM_MAX_SEGS], total = 0, before = 0;
+  for (int s = 0; s < n_seg; ++s) total += cost[s] = 230 + 60 * (((long long)seg_off[s + 1] - seg_off[s] + 63) / 64);
+  for (int s = 0; s < n_seg && n_seg > 1; ++s) {
+    const long long want = std::max(0LL, 3 - 4 * before / total);
+    CHECK(lv[s] == want, "%s n_seg=%d: level[%d] = %d, the definition gives %lld", what, n_seg, s, lv[s], want);
+    before += cost[s];
+  }
+  int32_t other[CF_STREAM_MAX_SEGS + 1], lv2[CF_STREAM_MAX_SEGS];
+  for (int s = 0; s <= CF_STREAM_MAX_SEGS; ++s) other[s] = s <= n_seg ? seg_off[s] : seg_off[n_seg] + 1000 * s;
+  cf_stream_levels(other, n_seg, lv2);
+  for (int s = 0; s < CF_STREAM_MAX_SEGS; ++s) CHECK(lv[s] == lv2[s], "%s n_seg=%d: level[%d] depends on offsets behind n_seg", what, n_seg, s);
+}
 
 static void check_plan(const std::vector<double>& z, const std::vector<double>* step, int G, double z_max, const char* what) {
   const int64_t n = (int64_t)z.size();
@@ -62,6 +96,7 @@ static void check_plan(const std::vector<double>& z, const std::vector<double>* 
     zm = std::max(zm, 1.0 + z[(size_t)i]);
   }
   CHECK(plan.max_step == ms && plan.zp1_max == zm, "%s: max_step %g (%g), zp1_max %g (%g)", what, plan.max_step, ms, plan.zp1_max, zm);
+  check_levels(plan.seg_off, plan.n_seg, what);
 }
 
 int main() {
@@ -130,6 +165,44 @@ int main() {
         }
       }
     CHECK(!(cf_stream_shift_bound(std::nan(""), 1.0, 1.0 + z_top, c, inv_step, &a) <= (double)CF_STREAM_GUARD_NODES), "NaN passes the guard");
+  }
+  // the wave-priority table: segment populations at the edges of a trip of 64 records and of a pair of trips, all in segment 0 of
+  // a grid of 520 nodes; SNe at z < 0.2 and z > 2.0 only on a grid of 4000 nodes (empty middle segments, whose cost is the table
+  // build alone); synthetic offsets for n_seg = 1 .. 8; the Pantheon+ shape of the issue (765 SNe in segment 0, ~134 in each other)
+  {
+    for (int n : {1, 63, 64, 65, 127, 128, 129, 191, 192, 193}) {
+      std::vector<double> z((size_t)n);
+      for (int i = 0; i < n; ++i) z[(size_t)i] = 0.01 + 0.3 * uni(rng);  // grid of 520 nodes to 2.36: nodes 2 .. 68, segment 0
+      check_plan(z, nullptr, 520, 2.36, "trip edges");
+      cf_stream_plan plan;
+      CHECK(cf_stream_assign(z.data(), nullptr, n, 520, 519.0 / 2.36, 2.36, plan) && plan.seg_off[1] == n, "trip edges n=%d: not all in segment 0", n);
+      int32_t lv[CF_STREAM_MAX_SEGS];
+      cf_stream_levels(plan.seg_off, plan.n_seg, lv);
+      CHECK(plan.n_seg == 2 && lv[0] == 3, "trip edges n=%d: n_seg %d, level[0] %d", n, plan.n_seg, lv[0]);
+    }
+    std::vector<double> z(70);
+    for (int i = 0; i < 70; ++i) z[(size_t)i] = i < 35 ? 0.2 * uni(rng) : 2.0 + 0.26 * uni(rng);
+    check_plan(z, nullptr, 4000, 2.36, "empty middle");
+    for (int n_seg = 1; n_seg <= CF_STREAM_MAX_SEGS; ++n_seg)
+      for (int shape = 0; shape < 5; ++shape) {
+        int32_t off[CF_STREAM_MAX_SEGS + 1] = {0};
+        for (int s = 0; s < CF_STREAM_MAX_SEGS; ++s) {
+          int n = 0;
+          if (shape == 0) n = 0;                                        // no SN anywhere
+          else if (shape == 1) n = s == 0 ? 765 : 134;                  // Pantheon+
+          else if (shape == 2) n = s == n_seg - 1 ? 1701 : 0;           // everything in the last segment
+          else if (shape == 3) n = s == 0 ? 1000000 : 1;                // everything but a few in the first
+          else n = (int)(uni(rng) * 400.0);
+          off[s + 1] = off[s] + (s < n_seg ? n : 0);
+        }
+        check_levels(off, n_seg, "synthetic offsets");
+      }
+    const int32_t pantheon[CF_STREAM_MAX_SEGS + 1] = {0, 765, 899, 1033, 1167, 1301, 1435, 1569, 1701};
+    int32_t lv[CF_STREAM_MAX_SEGS];
+    cf_stream_levels(pantheon, 8, lv);
+    std::printf("levels, Pantheon+ shape (765 SNe in segment 0, ~134 in each other): %d %d %d %d %d %d %d %d\n", lv[0], lv[1], lv[2], lv[3], lv[4],
+                lv[5], lv[6], lv[7]);
+    std::printf("levels: %d tables checked\n", level_tables);
   }
   std::printf("stream pack: %d plans checked, %d failures\n", plans, failures);
   return failures ? 1 : 0;
