@@ -264,6 +264,7 @@ EXPORTS = {
     "cf_solve_form": (C.c_int, [_I64, _I64, C.POINTER(C.c_int32 * 10)]),
     "cf_solve_frag_order": (C.c_int, [_VP, _I64]),
     "cf_small_blocks_form": (C.c_int, [_VP, _I64]),
+    "cf_last_residuals": (C.c_int, [_VP, _I64, _VP, C.POINTER(C.c_int32)]),
     "cf_interp_hermite": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _I64, _VP]),
     "cf_interp_pchip": (C.c_int, [_VP, _I64, _VP, _VP, _I64, _VP]),
     "cf_solve_triangular": (C.c_int, [_VP, _I64, _I64, _VP, _I64, _VP]),

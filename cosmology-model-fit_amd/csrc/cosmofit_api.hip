@@ -365,6 +365,10 @@ struct cf_handle {
   // than the previous one first waits (on the host) for that stream
   hipStream_t last_stream = nullptr;
   bool has_last = false;
+  // what cf_last_residuals reports: the batch size of the most recent evaluation and the layout its per-walker kernel was
+  // launched with (0 walker rows, 1 the small-batch solve's fragment order); -1 / 0 before the first evaluation
+  int64_t last_W = -1;
+  int last_layout = 0;
   // timing ring: per evaluation 4 events (before the walker kernel, behind it, behind the small-block / growth kernels, behind the solve)
   std::vector<hipEvent_t> ev;
   int timing_slots = 0, timing_stride = 1;
@@ -1233,6 +1237,29 @@ extern "C" int cf_solve_frag_order(cf_handle* h, int64_t W) {
   return small_frag_wanted(h, W) ? 1 : 0;
 }
 
+// The residual buffer as the per-walker kernel of the most recent evaluation left it (the solve kernels take it as const): the
+// first ceil(W / 16) * 16 * n_ld doubles, raw, and the layout that evaluation was LAUNCHED with (remembered by launch_eval, not
+// re-derived from W): 0 walker rows [w][n_ld], 1 the fragment order of delta_index (cosmofit_kernels.hip), which the caller undoes.
+extern "C" int cf_last_residuals(cf_handle* h, int64_t W, double* out, int32_t* layout) {
+  if (!h || !out || !layout) return fail(CF_ERR_INVALID, "cf_last_residuals: null argument");
+  if (!h->peers.empty()) return fail(CF_ERR_UNSUPPORTED, "cf_last_residuals: this handle spans several devices");
+  if (h->qsr) return fail(CF_ERR_UNSUPPORTED, "cf_last_residuals: a quasar handle");
+  if (h->d.n_sn == 0) return fail(CF_ERR_INVALID, "cf_last_residuals: this likelihood has no SN block");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (W < 1 || W != h->last_W)
+    return fail(CF_ERR_INVALID, "cf_last_residuals: W = " + std::to_string(W) + " is not the batch size of the last evaluation (" +
+                                    std::to_string(h->last_W) + ")");
+  DeviceScope on_device(h->device);
+  HIP_TRY(on_device.err);
+  if (h->has_last && h->last_stream != h->stream)  // the last evaluation ran on a caller's stream (order_behind_last)
+    HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  const size_t n = (size_t)((W + 15) / 16 * 16) * (size_t)h->d.n_ld;  // <= the workspace's 32-walker padding (ensure_workspace)
+  HIP_TRY(hipMemcpy(out, h->delta.p, n * 8, hipMemcpyDeviceToHost));
+  *layout = h->last_layout;
+  return CF_OK;
+}
+
 // The launch form of small_blocks_kernel for a batch of Wc walkers: what launch_eval launches and cf_small_blocks_form reports.
 // Sixteen lanes per walker, sixteen walkers per workgroup (4096 walkers = one wave per SIMD, issue-bound); below that the chip is
 // not full and the time is the serial chain of a lane: a whole wave per walker then (4 instead of 13 Gauss-Legendre nodes per
@@ -1584,6 +1611,8 @@ static int launch_eval(cf_handle* h, const double* th, int64_t Wc, double* out, 
   // a small batch of the production path: walker_fast_kernel writes the residuals in the fragment order the small-batch solve
   // kernel loads them in (one contiguous 1 KiB load per K-step pair instead of a 16-row gather: sn_fast_loop, FRAG)
   const bool frag_b = !dm_out && !mucorr_out && small_frag_b(h, Wc);
+  h->last_W = Wc;
+  h->last_layout = frag_b ? 1 : 0;
   if (h->qsr) {  // quasar likelihood: its own per-walker kernel writes the SN residuals (row layout) and the quasar / BAO chi^2
     double* th_copy = h->theta_on_host ? h->theta.as<double>() : nullptr;
     int rc = cf_qsr_launch(h->qsr, th, Wc, delta, extra, out_kind, th_copy, st);

@@ -511,6 +511,17 @@ class LikelihoodEngine:
         form["frag_order"] = rc
         return form
 
+    def last_residuals(self, W: int):
+        """(buffer, layout) of the most recent evaluation, which must have been of W walkers (cf_last_residuals): the SN residual
+        buffer as the per-walker kernel left it, float64 [ceil(W / 16) * 16, n_ld] raw, n_ld = n_sn rounded up to 64.  layout 0:
+        row w is walker w (entries n_sn .. n_ld - 1 zero padding); layout 1: the small-batch solve's fragment order -- element
+        (w, i) at flat index (w >> 4) * 16 * n_ld + (i >> 3) * 128 + ((i >> 1) & 3) * 32 + 2 * (w & 15) + (i & 1).  For tests."""
+        n_ld = (self.n_sn + 63) // 64 * 64
+        out = np.empty(((int(W) + 15) // 16 * 16, max(n_ld, 1)))
+        layout = C.c_int32(-1)
+        L.check(L.lib().cf_last_residuals(self._h, int(W), _ptr(out), C.byref(layout)))
+        return out, int(layout.value)
+
     def enable_timing(self, slots=1, stride=1):
         """Keep HIP-event timings of the last `slots` timed evaluations (0 = off); only every `stride`-th evaluation is timed."""
         L.check(L.lib().cf_enable_timing(self._h, int(slots)))

@@ -424,6 +424,14 @@ int cf_solve_frag_order(cf_handle* h, int64_t W);
  * 2048), 320 = one wave (only with sb_roles_max below W), 576 = two waves (the default up to 2048 walkers); the same bits in all
  * three.  0: the handle has none of these blocks (or is a quasar handle).  Negative: an error code (null handle, W < 1). */
 int cf_small_blocks_form(cf_handle* h, int64_t W);
+/* Debug query: the SN residual buffer as the per-walker kernel of the handle's most recent evaluation left it (the solve only reads
+ * it).  Waits for the handle's stream, then copies the first ceil(W / 16) * 16 * n_ld doubles to `out`, raw, and sets *layout to the
+ * layout that evaluation was launched with: 0 = walker rows (walker w at w * n_ld; rows n_sn .. n_ld - 1 are zero padding), 1 = the
+ * small-batch solve's fragment order, where element (w, i) sits at
+ *   (w >> 4) * 16 * n_ld + (i >> 3) * 128 + ((i >> 1) & 3) * 32 + 2 * (w & 15) + (i & 1).
+ * n_ld = n_sn rounded up to a multiple of 64.  CF_ERR_INVALID: a null argument, a handle without an SN block, a W that is not the
+ * batch size of the last evaluation (or no evaluation yet); CF_ERR_UNSUPPORTED: a handle on several devices, a quasar handle. */
+int cf_last_residuals(cf_handle* h, int64_t W, double* out, int32_t* layout);
 
 /* ---- stand-alone operators with the reference's signatures (host buffers) ---- */
 /* out[k] = Hermite(xq[k]; x, y, y_prime), linear extrapolation outside   interpolator.py:117-119 */
