@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/cosmofit.h"
+#include "cf_host.h"
 #include "cf_pack.h"
 #include "cf_stream_pack.h"
 #include "cosmofit_device.h"
@@ -236,28 +237,7 @@ static int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-int cf_set_error(int code, const std::string& msg) { return fail(code, msg); }  // for cosmofit_ensemble.hip
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return fail(CF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-  } while (0)
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int ensure(size_t need) {
-    if (need <= bytes) return 0;
-    if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-    HIP_TRY(hipMalloc(&p, need));
-    bytes = need;
-    return 0;
-  }
-  template <class T> T* as() const { return (T*)p; }
-};
+int cf_set_error(int code, const std::string& msg) { return fail(code, msg); }  // cf_host.h: the other translation units' way in
 
 struct PackedFactor {
   DevBuf frags, upd_off, diag_off;
@@ -664,24 +644,14 @@ static void fs8_points(const cf_dev_desc& d, const double* zs, int n, std::vecto
   }
 }
 
-// The calling thread's current device is the caller's business (a torch process has its own idea of it): every entry point switches
-// to the handle's device for its own HIP calls and switches back on the way out.  One hipGetDevice per call when the two agree.
-struct DeviceScope {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    if (cur != dev) {
-      err = hipSetDevice(dev);
-      if (err == hipSuccess) prev = cur;
-    }
-  }
-  ~DeviceScope() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  DeviceScope(const DeviceScope&) = delete;
-  DeviceScope& operator=(const DeviceScope&) = delete;
+// An entry point's hold on its handle: h->mu locked and the handle's device current (cf_host.h: DeviceScope) until it returns.
+// The helpers that need both take a `const HandleScope&` and reach the handle through it.
+struct HandleScope {
+  cf_handle* const h;
+  std::lock_guard<std::mutex> lock;
+  DeviceScope on_device;
+  const hipError_t err;
+  explicit HandleScope(cf_handle* handle) : h(handle), lock(h->mu), on_device(h->device), err(on_device.err) {}
 };
 
 // sqrt of the diagonal of inverse(inv_cov) (Gauss-Jordan with partial pivoting in extended precision): the errors of the BAO data
@@ -1288,9 +1258,8 @@ extern "C" int cf_small_blocks_form(cf_handle* h, int64_t W) {
 extern "C" int cf_enable_timing(cf_handle* h, int slots) {
   if (!h) return fail(CF_ERR_INVALID, "cf_enable_timing: null handle");
   if (slots < 0 || slots > 4096) return fail(CF_ERR_INVALID, "cf_enable_timing: slots must be in 0..4096");
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   while ((int)h->ev.size() < 4 * slots) {
     hipEvent_t e;
     HIP_TRY(hipEventCreate(&e));
@@ -1719,7 +1688,7 @@ static int launch_path(cf_handle* h, const double* d_theta, int64_t W, double* d
   if (ev) h->timed_calls++;
   h->last_stream = st;
   h->has_last = true;
-  HIP_TRY(hipGetLastError());
+  if (int launch_rc = cf_launch_status("launch_path")) return launch_rc;
   return 0;
 }
 
@@ -1737,9 +1706,8 @@ extern "C" int cf_eval_device(cf_handle* h, const double* d_theta, int64_t W, do
   if (!h->peers.empty())
     return fail(CF_ERR_INVALID, "cf_eval_device: this handle spans several devices; device-resident evaluation needs one handle per device");
   if (W == 0) return CF_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   if ((rc = ensure_workspace(h, W))) return rc;
   // exactly the caller's stream; NULL is HIP's default (null) stream, which is what torch reports as 0
   return launch_path(h, d_theta, W, d_out, out_kind, (hipStream_t)hip_stream, nullptr, nullptr, nullptr, nullptr);
@@ -1786,7 +1754,7 @@ static int wait_stream(hipStream_t st, bool worker_thread) {
 // staging blocks -- stage_in is no longer read by the finished evaluation (theta is read from the walker kernel's device copy
 // after the first kernel) and stage_out / the words are written only before the release.  Ordering against evaluations on a
 // CALLER's stream does not rely on this path: order_behind_last() drains h->stream at the switch.  A GPU fault in the drained tail
-// is reported by the next HIP call of the handle (launch_path ends in hipGetLastError), i.e. by the following evaluation.
+// is reported by the next HIP call of the handle (launch_path ends in cf_launch_status), i.e. by the following evaluation.
 // The spin holds h->mu (one caller per handle at a time is the documented threading model) and is bounded.
 static bool wait_done_flags(cf_handle* h) {
   static const bool on = [] { const char* e = getenv("CF_DONE_FLAG"); return !e || atoi(e) != 0; }();
@@ -1807,9 +1775,8 @@ static bool wait_done_flags(cf_handle* h) {
 // One replica, host buffers: stage through the handle's pinned block, run on the handle's stream, wait.
 static int eval_host_single(cf_handle* h, const double* theta, int64_t W, double* out, int out_kind, bool worker_thread) {
   int rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   if ((rc = ensure_workspace(h, W))) return rc;
   memcpy(h->stage_in.p, theta, (size_t)W * h->d.ndim * 8);
   // Small batches are latency-bound: the kernels then read theta from, and write the results to, the pinned (device-visible,
@@ -1893,9 +1860,8 @@ extern "C" int cf_eval_parts(cf_handle* h, const double* theta, int64_t W, doubl
   if (bao_theory && h->d.n_bao == 0) return fail(CF_ERR_INVALID, "cf_eval_parts: this likelihood has no BAO block");
   if (fs8_theory && h->d.n_fs8 == 0) return fail(CF_ERR_INVALID, "cf_eval_parts: this likelihood has no growth-rate block");
   if ((dm_obs || mu_corr || delta) && h->d.n_sn == 0) return fail(CF_ERR_INVALID, "cf_eval_parts: this likelihood has no SN block");
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   int rc;
   if ((rc = ensure_workspace(h, W))) return rc;
   const int64_t n = h->d.n_sn, n_ld = h->d.n_ld, nb = h->d.n_bao, nf = h->d.n_fs8;
@@ -1948,9 +1914,8 @@ extern "C" int cf_eval_table(cf_handle* h, const double* theta, int64_t W, doubl
   if (!h || !theta || !cum_dm || !dh) return fail(CF_ERR_INVALID, "cf_eval_table: null argument");
   if (h->qsr) return fail(CF_ERR_UNSUPPORTED, "cf_eval_table: a quasar handle; use cf_qsr_eval_parts");
   if (W <= 0 || W > 4096) return fail(CF_ERR_INVALID, "cf_eval_table: W must be in 1..4096");
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   int rc;
   if ((rc = ensure_workspace(h, W))) return rc;
   if ((rc = order_behind_last(h, h->stream))) return rc;
@@ -1967,7 +1932,7 @@ extern "C" int cf_eval_table(cf_handle* h, const double* theta, int64_t W, doubl
   const size_t lds = ((size_t)G + (G >> d.chunk_shift) + 2) * 16;
   hipLaunchKernelGGL(pick_walker(d.ez_model, d.fde), dim3((unsigned)W), dim3(512), lds, h->stream, d, h->theta.as<const double>(), W,
                      (double*)nullptr, (double*)nullptr, (double*)nullptr, (d2*)nullptr, tab.as<d2>());
-  HIP_TRY(hipGetLastError());
+  if (int launch_rc = cf_launch_status("cf_eval_table")) return launch_rc;
   std::vector<cf_d2> host((size_t)W * G);
   HIP_TRY(hipMemcpyAsync(host.data(), tab.p, host.size() * sizeof(cf_d2), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1986,9 +1951,8 @@ extern "C" int cf_eval_fs8_at(cf_handle* h, const double* theta, const double* z
     if (!(z[k] >= 0.0) || !(1.0 / (1.0 + z[k]) >= h->d.fs8_a_init))
       return fail(CF_ERR_INVALID, "cf_eval_fs8_at: redshifts must lie in a_init <= a <= 1");
   if (n == 0) return CF_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   int rc;
   if ((rc = ensure_workspace(h, 1))) return rc;
   if ((rc = order_behind_last(h, h->stream))) return rc;
@@ -2028,7 +1992,7 @@ extern "C" int cf_eval_fs8_at(cf_handle* h, const double* theta, const double* z
     hipLaunchKernelGGL(pick_growth(d.ez_model, d.fde, d.fs8_steps), dim3(1), dim3(256),
                        (size_t)(2 * (d.fs8_steps + 1) + 16 + CF_MAX_FS8 + 2 + 256) * 8, h->stream, d, h->theta.as<const double>(),
                        (int64_t)1, (const d2*)nodes.as<d2>(), extra.as<double>(), 0, (double*)nullptr, dout.as<double>());
-    HIP_TRY(hipGetLastError());
+    if (int launch_rc = cf_launch_status("cf_eval_fs8_at")) return launch_rc;
     HIP_TRY(hipMemcpyAsync(out + k0, dout.p, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));  // the host vectors and the staging buffers are reused by the next chunk
   }
@@ -2040,9 +2004,8 @@ extern "C" int cf_eval_hz(cf_handle* h, const double* theta, const double* z, in
   if (h->qsr) return fail(CF_ERR_UNSUPPORTED, "cf_eval_hz: a quasar handle; use cf_qsr_eval_parts");
   if (n < 0) return fail(CF_ERR_INVALID, "cf_eval_hz: n must be >= 0");
   if (n == 0) return CF_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   int rc;
   if ((rc = ensure_workspace(h, 1))) return rc;
   if ((rc = order_behind_last(h, h->stream))) return rc;
@@ -2052,7 +2015,7 @@ extern "C" int cf_eval_hz(cf_handle* h, const double* theta, const double* z, in
   HIP_TRY(hipMemcpyAsync(dz.p, z, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(pick_hz(h->d.ez_model, h->d.fde), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d,
                      h->theta.as<const double>(), dz.as<const double>(), n, dout.as<double>());
-  HIP_TRY(hipGetLastError());
+  if (int launch_rc = cf_launch_status("cf_eval_hz")) return launch_rc;
   HIP_TRY(hipMemcpyAsync(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return CF_OK;
@@ -2067,9 +2030,8 @@ extern "C" int cf_eval_bao_at(cf_handle* h, const double* theta, const double* z
     if (qty[k] < 0 || qty[k] > 3) return fail(CF_ERR_INVALID, "cf_eval_bao_at: qty must be 0 (D_V), 1 (D_M), 2 (D_H) or 3 (F_AP)");
   }
   if (n == 0) return CF_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   int rc;
   if ((rc = ensure_workspace(h, 1))) return rc;
   if ((rc = order_behind_last(h, h->stream))) return rc;
@@ -2100,7 +2062,7 @@ extern "C" int cf_eval_bao_at(cf_handle* h, const double* theta, const double* z
                        (double*)nullptr, (double*)nullptr, (double*)nullptr, nodes.as<d2>(), (d2*)nullptr);
     hipLaunchKernelGGL(pick_small_blocks(d.ez_model, d.fde, 16), dim3(1), dim3(256), 0, h->stream, d, h->theta.as<const double>(), (int64_t)1,
                        (const d2*)nodes.as<d2>(), extra.as<double>(), (double*)nullptr, dout.as<double>());
-    HIP_TRY(hipGetLastError());
+    if (int launch_rc = cf_launch_status("cf_eval_bao_at")) return launch_rc;
     HIP_TRY(hipMemcpyAsync(out + k0, dout.p, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));  // `base` and the staging buffers are reused by the next chunk
   }
@@ -2129,7 +2091,7 @@ static int interp_common(const double* xq, int64_t nq, const double* x, const do
   }
   hipLaunchKernelGGL(interp_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, dxq.as<const double>(), nq,
                      dx.as<const double>(), dy.as<const double>(), dyp.as<const double>(), n, dout.as<double>(), mode);
-  HIP_TRY(hipGetLastError());
+  if (int launch_rc = cf_launch_status("cf_interp")) return launch_rc;
   HIP_TRY(hipMemcpy(out, dout.p, (size_t)nq * 8, hipMemcpyDeviceToHost));
   return CF_OK;
 }
@@ -2171,7 +2133,7 @@ extern "C" int cf_solve_triangular(const double* L, int64_t n, int64_t ld, const
   if ((rc = launch_trsm(epi0.as<const cf_epilogue>(), (int)n_pad, (int)n_ld, 0, pf.dev, dth.as<const double>(), nrhs, delta.as<const double>(), ypk.as<d2>(), nullptr,
                         dout.as<double>(), (int)CF_OUT_CHI2, nf.as<unsigned long long>(), (hipStream_t)0, nullptr)))
     return rc;
-  HIP_TRY(hipGetLastError());
+  if (int launch_rc = cf_launch_status("cf_solve_triangular")) return launch_rc;
   HIP_TRY(hipMemcpy(out, dout.p, (size_t)nrhs * 8, hipMemcpyDeviceToHost));
   return CF_OK;
 }
@@ -2206,7 +2168,7 @@ static int selftest_log10(const double* x, int64_t n, double* out, int mode, con
   HIP_TRY(hipMemcpy(dx.p, x, (size_t)n * 8, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(log10_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx.as<const double>(), n,
                      dout.as<double>(), mode, tab.as<const cf_d2>());
-  HIP_TRY(hipGetLastError());
+  if (int launch_rc = cf_launch_status(fn)) return launch_rc;
   HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost));
   return CF_OK;
 }
@@ -2227,7 +2189,7 @@ extern "C" int cf_selftest_pos_ops(const double* a, const double* b, int64_t n, 
   HIP_TRY(hipMemcpy(db.p, b, (size_t)n * 8, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(pos_ops_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, da.as<const double>(),
                      db.as<const double>(), n, dout.as<double>());
-  HIP_TRY(hipGetLastError());
+  if (int launch_rc = cf_launch_status("cf_selftest_pos_ops")) return launch_rc;
   HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost));
   return CF_OK;
 }
@@ -2285,9 +2247,8 @@ extern "C" int cf_qsr_eval_parts(cf_handle* h, const double* theta, int64_t W, d
   if (mu_sn && h->d.n_sn == 0) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: this likelihood has no SN block");
   const int64_t nq = cf_qsr_n_qsr(h->qsr), nb = cf_qsr_n_bao(h->qsr), n = h->d.n_sn;
   if (bao_theory && nb == 0) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: this likelihood has no BAO block");
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   int rc;
   if ((rc = ensure_workspace(h, W))) return rc;
   DevBuf parts, snb, ms, mq, bt;
@@ -2482,9 +2443,8 @@ extern "C" int cf_derived_device(cf_handle* h, const double* d_theta, int64_t S,
   if (S < 0 || S > CF_DQ_MAX_ROWS) return fail(CF_ERR_INVALID, "cf_derived_device: S out of range");
   if (S == 0) return CF_OK;
   if (!d_theta || !d_out) return fail(CF_ERR_INVALID, "cf_derived_device: null argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   return cf_derived_launch(h->d, a, d_theta, S, d_out, (hipStream_t)hip_stream);
 }
 
@@ -2496,9 +2456,8 @@ extern "C" int cf_curves_device(cf_handle* h, const double* d_theta, int64_t S, 
   if (S < 0 || S > CF_DQ_MAX_ROWS) return fail(CF_ERR_INVALID, "cf_curves_device: S out of range");
   if (S == 0) return CF_OK;
   if (!d_theta || !d_z || !d_out) return fail(CF_ERR_INVALID, "cf_curves_device: null argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
   return cf_curves_launch(h->d, d_theta, S, code, d_z, nz, d_out, (hipStream_t)hip_stream);
 }
 
@@ -2514,21 +2473,12 @@ extern "C" int cf_derived(cf_handle* h, const double* theta, int64_t S, const in
   if (S < 0 || S > CF_DQ_MAX_ROWS) return fail(CF_ERR_INVALID, "cf_derived: S out of range");
   if (S == 0) return CF_OK;
   if (!theta || !out) return fail(CF_ERR_INVALID, "cf_derived: null argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
-  const int64_t chunk = std::min<int64_t>(S, CF_DQ_HOST_CHUNK);
-  const int ndim = h->d.ndim;
-  DevBuf dth, dout;
-  if (dth.ensure((size_t)chunk * ndim * 8) || dout.ensure((size_t)chunk * n_q * 8)) return CF_ERR_HIP;
-  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-    const int64_t m = std::min(chunk, S - s0);
-    HIP_TRY(hipMemcpyAsync(dth.p, theta + s0 * ndim, (size_t)m * ndim * 8, hipMemcpyHostToDevice, h->stream));
-    if ((rc = cf_derived_launch(h->d, a, dth.as<const double>(), m, dout.as<double>(), h->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(out + s0 * n_q, dout.p, (size_t)m * n_q * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return CF_OK;
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  RowStage rows(h->stream, std::min<int64_t>(S, CF_DQ_HOST_CHUNK));
+  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
+  double* dout = rows.out(out, (size_t)n_q * 8);
+  return rows.run(S, [&](int64_t, int64_t m) { return cf_derived_launch(h->d, a, dth, m, dout, h->stream); });
 }
 
 extern "C" int cf_curves(cf_handle* h, const double* theta, int64_t S, int32_t code, const double* z, int32_t nz, double* out) {
@@ -2538,22 +2488,17 @@ extern "C" int cf_curves(cf_handle* h, const double* theta, int64_t S, int32_t c
   if (S < 0 || S > CF_DQ_MAX_ROWS) return fail(CF_ERR_INVALID, "cf_curves: S out of range");
   if (S == 0) return CF_OK;
   if (!theta || !z || !out) return fail(CF_ERR_INVALID, "cf_curves: null argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
-  const int64_t chunk = std::min<int64_t>(S, std::max<int64_t>(1, CF_DQ_HOST_CHUNK * 16 / nz));
-  const int ndim = h->d.ndim;
-  DevBuf dth, dz, dout;
-  if (dth.ensure((size_t)chunk * ndim * 8) || dz.ensure((size_t)nz * 8) || dout.ensure((size_t)chunk * nz * 8)) return CF_ERR_HIP;
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  RowStage rows(h->stream, std::min<int64_t>(S, std::max<int64_t>(1, CF_DQ_HOST_CHUNK * 16 / nz)));
+  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
+  double* dout = rows.out(out, (size_t)nz * 8);
+  DevBuf dz;
+  if (dz.ensure((size_t)nz * 8)) return CF_ERR_HIP;
   HIP_TRY(hipMemcpyAsync(dz.p, z, (size_t)nz * 8, hipMemcpyHostToDevice, h->stream));
-  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-    const int64_t m = std::min(chunk, S - s0);
-    HIP_TRY(hipMemcpyAsync(dth.p, theta + s0 * ndim, (size_t)m * ndim * 8, hipMemcpyHostToDevice, h->stream));
-    if ((rc = cf_curves_launch(h->d, dth.as<const double>(), m, code, dz.as<const double>(), nz, dout.as<double>(), h->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(out + s0 * (int64_t)nz, dout.p, (size_t)m * nz * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return CF_OK;
+  return rows.run(S, [&](int64_t, int64_t m) {
+    return cf_curves_launch(h->d, dth, m, code, dz.as<const double>(), nz, dout, h->stream);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2564,28 +2509,42 @@ extern "C" int cf_curves(cf_handle* h, const double* theta, int64_t S, int32_t c
 #define CF_RESID_MAX_ROWS (((int64_t)1 << 31) - 1)
 #define CF_RESID_MAX_CHUNK 65536
 
-extern "C" int cf_resid_check_args(int64_t n_sn, int32_t n_bao, int32_t is_quasar, int32_t n_devices, const void* theta, int64_t S,
-                                   int32_t block, const double* thresholds, int32_t n_thr, const void* sample, const void* chi2_blocks,
-                                   const cf_resid_acc* acc) {
-  const std::string F = "cf_resid: ";
-  if (is_quasar) return fail(CF_ERR_UNSUPPORTED, F + "a quasar handle has no accessor path to take the residuals from");
-  if (n_devices > 1) return fail(CF_ERR_UNSUPPORTED, F + "this handle spans several devices; use one handle per device");
+// What cf_resid and cf_infl check alike (F: "<entry point>: ").  Their refusals of a quasar or multi-device handle differ in the
+// return code and their accumulator messages in the wording, so those stay with each.
+static int check_block(const std::string& F, int64_t n_sn, int32_t n_bao, int32_t block) {
   if (block != CF_RB_SN && block != CF_RB_BAO) return fail(CF_ERR_INVALID, F + "block must be CF_RB_SN or CF_RB_BAO");
   if (block == CF_RB_SN && n_sn <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no SN block");
   if (block == CF_RB_BAO && n_bao <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no BAO block");
+  return CF_OK;
+}
+static int check_rows_thresholds(const std::string& F, int64_t S, const double* thresholds, int32_t n_thr) {
   if (S < 0 || S > CF_RESID_MAX_ROWS) return fail(CF_ERR_INVALID, F + "S out of range");
   if (n_thr < 0 || n_thr > CF_RESID_MAX_THR) return fail(CF_ERR_INVALID, F + "n_thr must be in 0..4");
   if (n_thr > 0 && !thresholds) return fail(CF_ERR_INVALID, F + "null thresholds");
   for (int k = 0; k < n_thr; ++k)
     if (!std::isfinite(thresholds[k]) || thresholds[k] < 0.0) return fail(CF_ERR_INVALID, F + "thresholds must be finite and >= 0");
+  return CF_OK;
+}
+static bool acc_lacks_an_array(const cf_resid_acc* acc, int32_t n_thr) {
+  return !acc->w_sum || !acc->mean || !acc->m2 || !acc->n_used || !acc->n_skipped || (n_thr > 0 && !acc->exceed);
+}
+
+extern "C" int cf_resid_check_args(int64_t n_sn, int32_t n_bao, int32_t is_quasar, int32_t n_devices, const void* theta, int64_t S,
+                                   int32_t block, const double* thresholds, int32_t n_thr, const void* sample, const void* chi2_blocks,
+                                   const cf_resid_acc* acc) {
+  const std::string F = "cf_resid: ";
+  int rc;
+  if (is_quasar) return fail(CF_ERR_UNSUPPORTED, F + "a quasar handle has no accessor path to take the residuals from");
+  if (n_devices > 1) return fail(CF_ERR_UNSUPPORTED, F + "this handle spans several devices; use one handle per device");
+  if ((rc = check_block(F, n_sn, n_bao, block))) return rc;
+  if ((rc = check_rows_thresholds(F, S, thresholds, n_thr))) return rc;
   if (!sample && !chi2_blocks && !acc) return fail(CF_ERR_INVALID, F + "no output requested");
   if (acc) {
     const int64_t n = block == CF_RB_SN ? n_sn : n_bao;
     if (acc->struct_size != (int32_t)sizeof(cf_resid_acc)) return fail(CF_ERR_INVALID, F + "cf_resid_acc.struct_size mismatch");
     if (acc->n != n) return fail(CF_ERR_INVALID, F + "cf_resid_acc.n is not the number of data of the block");
     if (acc->n_thr != n_thr) return fail(CF_ERR_INVALID, F + "cf_resid_acc.n_thr differs from n_thr");
-    if (!acc->w_sum || !acc->mean || !acc->m2 || !acc->n_used || !acc->n_skipped || (n_thr > 0 && !acc->exceed))
-      return fail(CF_ERR_INVALID, F + "null array in cf_resid_acc");
+    if (acc_lacks_an_array(acc, n_thr)) return fail(CF_ERR_INVALID, F + "null array in cf_resid_acc");
   }
   if (S > 0 && !theta) return fail(CF_ERR_INVALID, F + "null theta");
   return CF_OK;
@@ -2607,17 +2566,21 @@ extern "C" int cf_resid_sigma(cf_handle* h, int32_t block, double* out) {
   return CF_OK;
 }
 
-extern "C" int cf_resid_set_chunk(cf_handle* h, int64_t rows) {
-  if (!h) return fail(CF_ERR_INVALID, "cf_resid_set_chunk: null handle");
-  if (rows < 0 || rows > CF_RESID_MAX_CHUNK) return fail(CF_ERR_INVALID, "cf_resid_set_chunk: rows must be in 0..65536");
+// cf_resid_set_chunk, cf_mock_set_chunk, cf_infl_set_chunk: rows per chunk of one of the three loops over the workspace.
+static int set_chunk(cf_handle* h, int64_t cf_handle::*field, int64_t rows, const char* fn) {
+  if (!h) return fail(CF_ERR_INVALID, std::string(fn) + ": null handle");
+  if (rows < 0 || rows > CF_RESID_MAX_CHUNK) return fail(CF_ERR_INVALID, std::string(fn) + ": rows must be in 0..65536");
   std::lock_guard<std::mutex> lk(h->mu);
-  h->resid_chunk = rows;
+  h->*field = rows;
   return CF_OK;
 }
 
+extern "C" int cf_resid_set_chunk(cf_handle* h, int64_t rows) { return set_chunk(h, &cf_handle::resid_chunk, rows, "cf_resid_set_chunk"); }
+
 // Buffers for chunks of `rows` rows and the device copy of sigma.  Growing frees buffers an evaluation on a caller's stream may
 // still use: synchronise first, as ensure_workspace does.
-static int resid_prepare(cf_handle* h, int64_t rows) {
+static int resid_prepare(const HandleScope& hs, int64_t rows) {
+  cf_handle* const h = hs.h;
   if (!h->sigma_uploaded) {
     int rc;
     if (!h->sigma_sn_host.empty() && (rc = upload_vec(h->sigma_sn, h->sigma_sn_host.data(), (int64_t)h->sigma_sn_host.size()))) return rc;
@@ -2635,13 +2598,15 @@ static int resid_prepare(cf_handle* h, int64_t rows) {
   return 0;
 }
 
-// Arguments checked, h->mu held, the handle's device current.  Device pointers throughout.
-static int resid_run(cf_handle* h, const double* d_theta, int64_t S, const double* d_w, int32_t block, const double* thresholds,
-                     int32_t n_thr, double* d_sample, double* d_chi2_blocks, const cf_resid_acc* acc, hipStream_t st) {
+// Arguments checked.  Device pointers throughout.
+static int resid_run(const HandleScope& hs, const double* d_theta, int64_t S, const double* d_w, int32_t block,
+                     const double* thresholds, int32_t n_thr, double* d_sample, double* d_chi2_blocks, const cf_resid_acc* acc,
+                     hipStream_t st) {
+  cf_handle* const h = hs.h;
   int rc;
   const int64_t chunk = std::min<int64_t>(S, h->resid_chunk > 0 ? h->resid_chunk : CF_RESID_CHUNK);
   if ((rc = ensure_workspace(h, chunk))) return rc;
-  if ((rc = resid_prepare(h, chunk))) return rc;
+  if ((rc = resid_prepare(hs, chunk))) return rc;
   const cf_dev_desc& d = h->d;
   const bool want_blocks = d_chi2_blocks != nullptr;
   cf_resid_src src{};
@@ -2689,11 +2654,45 @@ extern "C" int cf_resid_device(cf_handle* h, const double* d_theta, int64_t S, c
   int rc = resid_check(h, d_theta, S, block, thresholds, n_thr, d_sample, d_chi2_blocks, acc);
   if (rc) return rc;
   if (S == 0) return CF_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
-  return resid_run(h, d_theta, S, d_w, block, thresholds, n_thr, d_sample, d_chi2_blocks, acc, (hipStream_t)hip_stream);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  return resid_run(hs, d_theta, S, d_w, block, thresholds, n_thr, d_sample, d_chi2_blocks, acc, (hipStream_t)hip_stream);
 }
+
+// The device twin of a host cf_resid_acc: up once, continued piece by piece on the device, down at the end.
+struct HostAccTwin {
+  DevBuf w, mean, m2, ex, used, skip;
+  cf_resid_acc dev{};
+  cf_resid_acc* host = nullptr;
+  int up(cf_resid_acc* acc, hipStream_t st) {
+    host = acc;
+    if (!acc) return 0;
+    const size_t nb = (size_t)acc->n * 8, ne = nb * (size_t)acc->n_thr;
+    dev = *acc;
+    if (w.ensure(nb) || mean.ensure(nb) || m2.ensure(nb) || used.ensure(nb) || skip.ensure(nb) || (ne && ex.ensure(ne))) return CF_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(w.p, acc->w_sum, nb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(mean.p, acc->mean, nb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m2.p, acc->m2, nb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(used.p, acc->n_used, nb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(skip.p, acc->n_skipped, nb, hipMemcpyHostToDevice, st));
+    if (ne) HIP_TRY(hipMemcpyAsync(ex.p, acc->exceed, ne, hipMemcpyHostToDevice, st));
+    dev.w_sum = w.as<double>(); dev.mean = mean.as<double>(); dev.m2 = m2.as<double>(); dev.exceed = ex.as<double>();
+    dev.n_used = used.as<int64_t>(); dev.n_skipped = skip.as<int64_t>();
+    return 0;
+  }
+  int down() {
+    if (!host) return 0;
+    const size_t nb = (size_t)host->n * 8, ne = nb * (size_t)host->n_thr;
+    HIP_TRY(hipMemcpy(host->w_sum, w.p, nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host->mean, mean.p, nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host->m2, m2.p, nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host->n_used, used.p, nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host->n_skipped, skip.p, nb, hipMemcpyDeviceToHost));
+    if (ne) HIP_TRY(hipMemcpy(host->exceed, ex.p, ne, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  const cf_resid_acc* ptr() const { return host ? &dev : nullptr; }
+};
 
 // Host-buffer twin: rows in pieces through temporary device buffers on the handle's own stream; the accumulator goes to the
 // device once, is continued there piece by piece, and comes back at the end.
@@ -2704,52 +2703,20 @@ extern "C" int cf_resid(cf_handle* h, const double* theta, int64_t S, const doub
   int rc = resid_check(h, theta, S, block, thresholds, n_thr, sample, chi2_blocks, acc);
   if (rc) return rc;
   if (S == 0) return CF_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
-  const int64_t piece = std::min<int64_t>(S, CF_RESID_HOST_PIECE);
-  const int ndim = h->d.ndim;
-  DevBuf dth, dw, ds, db, a_w, a_mean, a_m2, a_ex, a_used, a_skip;
-  if (dth.ensure((size_t)piece * ndim * 8)) return CF_ERR_HIP;
-  if (w && dw.ensure((size_t)piece * 8)) return CF_ERR_HIP;
-  if (sample && ds.ensure((size_t)piece * CF_RS_NCOL * 8)) return CF_ERR_HIP;
-  if (chi2_blocks && db.ensure((size_t)piece * 10 * 8)) return CF_ERR_HIP;
-  cf_resid_acc dacc{};
-  if (acc) {
-    const size_t nb = (size_t)acc->n * 8;
-    dacc = *acc;
-    if (a_w.ensure(nb) || a_mean.ensure(nb) || a_m2.ensure(nb) || a_used.ensure(nb) || a_skip.ensure(nb)) return CF_ERR_HIP;
-    if (n_thr > 0 && a_ex.ensure(nb * n_thr)) return CF_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(a_w.p, acc->w_sum, nb, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(a_mean.p, acc->mean, nb, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(a_m2.p, acc->m2, nb, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(a_used.p, acc->n_used, nb, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(a_skip.p, acc->n_skipped, nb, hipMemcpyHostToDevice, h->stream));
-    if (n_thr > 0) HIP_TRY(hipMemcpyAsync(a_ex.p, acc->exceed, nb * n_thr, hipMemcpyHostToDevice, h->stream));
-    dacc.w_sum = a_w.as<double>(); dacc.mean = a_mean.as<double>(); dacc.m2 = a_m2.as<double>(); dacc.exceed = a_ex.as<double>();
-    dacc.n_used = a_used.as<int64_t>(); dacc.n_skipped = a_skip.as<int64_t>();
-  }
-  for (int64_t s0 = 0; s0 < S; s0 += piece) {
-    const int64_t m = std::min(piece, S - s0);
-    HIP_TRY(hipMemcpyAsync(dth.p, theta + s0 * ndim, (size_t)m * ndim * 8, hipMemcpyHostToDevice, h->stream));
-    if (w) HIP_TRY(hipMemcpyAsync(dw.p, w + s0, (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
-    if ((rc = resid_run(h, dth.as<const double>(), m, w ? dw.as<const double>() : nullptr, block, thresholds, n_thr,
-                        sample ? ds.as<double>() : nullptr, chi2_blocks ? db.as<double>() : nullptr, acc ? &dacc : nullptr, h->stream)))
-      return rc;
-    if (sample) HIP_TRY(hipMemcpyAsync(sample + s0 * CF_RS_NCOL, ds.p, (size_t)m * CF_RS_NCOL * 8, hipMemcpyDeviceToHost, h->stream));
-    if (chi2_blocks) HIP_TRY(hipMemcpyAsync(chi2_blocks + s0 * 10, db.p, (size_t)m * 10 * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  if (acc) {
-    const size_t nb = (size_t)acc->n * 8;
-    HIP_TRY(hipMemcpy(acc->w_sum, a_w.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(acc->mean, a_mean.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(acc->m2, a_m2.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(acc->n_used, a_used.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(acc->n_skipped, a_skip.p, nb, hipMemcpyDeviceToHost));
-    if (n_thr > 0) HIP_TRY(hipMemcpy(acc->exceed, a_ex.p, nb * n_thr, hipMemcpyDeviceToHost));
-  }
-  return CF_OK;
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  RowStage rows(h->stream, std::min<int64_t>(S, CF_RESID_HOST_PIECE));
+  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
+  const double* dw = rows.in(w, 8);
+  double* ds = rows.out(sample, (size_t)CF_RS_NCOL * 8);
+  double* db = rows.out(chi2_blocks, 10 * 8);
+  HostAccTwin dacc;
+  if ((rc = dacc.up(acc, h->stream))) return rc;
+  if ((rc = rows.run(S, [&](int64_t, int64_t m) {
+         return resid_run(hs, dth, m, dw, block, thresholds, n_thr, ds, db, dacc.ptr(), h->stream);
+       })))
+    return rc;
+  return dacc.down();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2789,21 +2756,16 @@ static int mock_check(cf_handle* h, const cf_mock_set* set, const void* theta, i
                             S, mock, out_kind, out);
 }
 
-extern "C" int cf_mock_set_chunk(cf_handle* h, int64_t rows) {
-  if (!h) return fail(CF_ERR_INVALID, "cf_mock_set_chunk: null handle");
-  if (rows < 0 || rows > CF_RESID_MAX_CHUNK) return fail(CF_ERR_INVALID, "cf_mock_set_chunk: rows must be in 0..65536");
-  std::lock_guard<std::mutex> lk(h->mu);
-  h->mock_chunk = rows;
-  return CF_OK;
-}
+extern "C" int cf_mock_set_chunk(cf_handle* h, int64_t rows) { return set_chunk(h, &cf_handle::mock_chunk, rows, "cf_mock_set_chunk"); }
 
-// Arguments checked, h->mu held, the handle's device current.  Device pointers throughout (the set's arrays too).
-static int mock_run(cf_handle* h, const cf_mock_set& set, const double* d_theta, int64_t S, const int32_t* d_mock, int32_t out_kind,
-                    double* d_out, double* d_cross, hipStream_t st) {
+// Arguments checked.  Device pointers throughout (the set's arrays too).
+static int mock_run(const HandleScope& hs, const cf_mock_set& set, const double* d_theta, int64_t S, const int32_t* d_mock,
+                    int32_t out_kind, double* d_out, double* d_cross, hipStream_t st) {
+  cf_handle* const h = hs.h;
   int rc;
   const int64_t chunk = std::min<int64_t>(S, h->mock_chunk > 0 ? h->mock_chunk : CF_MOCK_CHUNK);
   if ((rc = ensure_workspace(h, chunk))) return rc;
-  if ((rc = resid_prepare(h, chunk))) return rc;
+  if ((rc = resid_prepare(hs, chunk))) return rc;
   const cf_dev_desc& d = h->d;
   cf_mock_args a{};
   a.sn_rows = h->delta.as<const double>();
@@ -2833,10 +2795,9 @@ extern "C" int cf_mock_eval_device(cf_handle* h, const cf_mock_set* set, const d
   int rc = mock_check(h, set, d_theta, S, d_mock, out_kind, d_out);
   if (rc) return rc;
   if (S == 0) return CF_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
-  return mock_run(h, *set, d_theta, S, d_mock, out_kind, d_out, d_cross, (hipStream_t)hip_stream);
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  return mock_run(hs, *set, d_theta, S, d_mock, out_kind, d_out, d_cross, (hipStream_t)hip_stream);
 }
 
 // Host-buffer twin: the set goes to the device once, the rows in pieces through temporary device buffers on the handle's stream.
@@ -2845,12 +2806,10 @@ extern "C" int cf_mock_eval(cf_handle* h, const cf_mock_set* set, const double* 
   int rc = mock_check(h, set, theta, S, mock, out_kind, out);
   if (rc) return rc;
   if (S == 0) return CF_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
-  const int64_t piece = std::min<int64_t>(S, CF_RESID_HOST_PIECE), K = set->n_mocks;
-  const int ndim = h->d.ndim;
-  DevBuf gs, gb, gc, cc, dth, dmk, dout, dcr;
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  const int64_t K = set->n_mocks;
+  DevBuf gs, gb, gc, cc;
   cf_mock_set dset = *set;
   if (set->n_sn) {
     if (gs.ensure((size_t)K * set->n_sn * 8)) return CF_ERR_HIP;
@@ -2870,20 +2829,12 @@ extern "C" int cf_mock_eval(cf_handle* h, const cf_mock_set* set, const double* 
   if (cc.ensure((size_t)K * 8)) return CF_ERR_HIP;
   HIP_TRY(hipMemcpyAsync(cc.p, set->c, (size_t)K * 8, hipMemcpyHostToDevice, h->stream));
   dset.c = cc.as<const double>();
-  if (dth.ensure((size_t)piece * ndim * 8) || dmk.ensure((size_t)piece * 4) || dout.ensure((size_t)piece * 8)) return CF_ERR_HIP;
-  if (cross && dcr.ensure((size_t)piece * 3 * 8)) return CF_ERR_HIP;
-  for (int64_t s0 = 0; s0 < S; s0 += piece) {
-    const int64_t m = std::min(piece, S - s0);
-    HIP_TRY(hipMemcpyAsync(dth.p, theta + s0 * ndim, (size_t)m * ndim * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dmk.p, mock + s0, (size_t)m * 4, hipMemcpyHostToDevice, h->stream));
-    if ((rc = mock_run(h, dset, dth.as<const double>(), m, dmk.as<const int32_t>(), out_kind, dout.as<double>(),
-                       cross ? dcr.as<double>() : nullptr, h->stream)))
-      return rc;
-    HIP_TRY(hipMemcpyAsync(out + s0, dout.p, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
-    if (cross) HIP_TRY(hipMemcpyAsync(cross + s0 * 3, dcr.p, (size_t)m * 3 * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return CF_OK;
+  RowStage rows(h->stream, std::min<int64_t>(S, CF_RESID_HOST_PIECE));
+  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
+  const int32_t* dmk = rows.in(mock, 4);
+  double* dout = rows.out(out, 8);
+  double* dcr = rows.out(cross, 3 * 8);
+  return rows.run(S, [&](int64_t, int64_t m) { return mock_run(hs, dset, dth, m, dmk, out_kind, dout, dcr, h->stream); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3101,8 +3052,7 @@ static int infl_check_acc(const std::string& F, const char* name, const cf_resid
   if (acc->struct_size != (int32_t)sizeof(cf_resid_acc)) return fail(CF_ERR_INVALID, A + ".struct_size mismatch");
   if (acc->n != n) return fail(CF_ERR_INVALID, A + ".n is not the number of data of the block");
   if (acc->n_thr != n_thr) return fail(CF_ERR_INVALID, A + (n_thr ? ".n_thr differs from n_thr" : ".n_thr must be 0"));
-  if (!acc->w_sum || !acc->mean || !acc->m2 || !acc->n_used || !acc->n_skipped || (n_thr > 0 && !acc->exceed))
-    return fail(CF_ERR_INVALID, A + " has a null array");
+  if (acc_lacks_an_array(acc, n_thr)) return fail(CF_ERR_INVALID, A + " has a null array");
   return CF_OK;
 }
 
@@ -3113,22 +3063,16 @@ extern "C" int cf_infl_check_args(int64_t n_sn, int32_t n_bao, int32_t is_quasar
   const std::string F = "cf_infl: ";
   if (is_quasar) return fail(CF_ERR_INVALID, F + "a quasar handle has no accessor path to take the residuals from");
   if (n_devices > 1) return fail(CF_ERR_INVALID, F + "this handle spans several devices; use one handle per device");
-  if (block != CF_RB_SN && block != CF_RB_BAO) return fail(CF_ERR_INVALID, F + "block must be CF_RB_SN or CF_RB_BAO");
-  if (block == CF_RB_SN && n_sn <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no SN block");
-  if (block == CF_RB_BAO && n_bao <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no BAO block");
+  int rc;
+  if ((rc = check_block(F, n_sn, n_bao, block))) return rc;
   const int64_t n = block == CF_RB_SN ? n_sn : n_bao;
   if (!has_prec) return fail(CF_ERR_INVALID, F + "null cf_prec");
   if (prec_n != n) return fail(CF_ERR_INVALID, F + "cf_prec.n is not the number of data of the block");
   if (prec_device != handle_device) return fail(CF_ERR_INVALID, F + "the cf_prec lives on another device than the handle");
-  if (S < 0 || S > CF_RESID_MAX_ROWS) return fail(CF_ERR_INVALID, F + "S out of range");
-  if (n_thr < 0 || n_thr > CF_RESID_MAX_THR) return fail(CF_ERR_INVALID, F + "n_thr must be in 0..4");
-  if (n_thr > 0 && !thresholds) return fail(CF_ERR_INVALID, F + "null thresholds");
-  for (int k = 0; k < n_thr; ++k)
-    if (!std::isfinite(thresholds[k]) || thresholds[k] < 0.0) return fail(CF_ERR_INVALID, F + "thresholds must be finite and >= 0");
+  if ((rc = check_rows_thresholds(F, S, thresholds, n_thr))) return rc;
   if (out && out->struct_size != (int32_t)sizeof(cf_infl_out)) return fail(CF_ERR_INVALID, F + "cf_infl_out.struct_size mismatch");
   const bool any_out = out && (out->g || out->contrib || out->z || out->loo || out->sample);
   if (!any_out && !acc_z && !acc_contrib) return fail(CF_ERR_INVALID, F + "no output requested");
-  int rc;
   if (acc_z && (rc = infl_check_acc(F, "acc_z", acc_z, n, n_thr))) return rc;
   if (acc_contrib && (rc = infl_check_acc(F, "acc_contrib", acc_contrib, n, 0))) return rc;
   if (S > 0 && !theta) return fail(CF_ERR_INVALID, F + "null theta");
@@ -3142,17 +3086,12 @@ static int infl_check(cf_handle* h, cf_prec* prec, const void* theta, int64_t S,
                             prec ? prec->n : 0, prec ? prec->device : 0, theta, S, block, thresholds, n_thr, out, acc_z, acc_contrib);
 }
 
-extern "C" int cf_infl_set_chunk(cf_handle* h, int64_t rows) {
-  if (!h) return fail(CF_ERR_INVALID, "cf_infl_set_chunk: null handle");
-  if (rows < 0 || rows > CF_RESID_MAX_CHUNK) return fail(CF_ERR_INVALID, "cf_infl_set_chunk: rows must be in 0..65536");
-  std::lock_guard<std::mutex> lk(h->mu);
-  h->infl_chunk = rows;
-  return CF_OK;
-}
+extern "C" int cf_infl_set_chunk(cf_handle* h, int64_t rows) { return set_chunk(h, &cf_handle::infl_chunk, rows, "cf_infl_set_chunk"); }
 
 // The chunk buffers of g and of the contrib / z rows.  Growing frees buffers an earlier call on a caller's stream may still use:
 // synchronise first, as resid_prepare does.
-static int infl_prepare(cf_handle* h, int64_t rows, int64_t n, bool need_g, bool need_contrib, bool need_z) {
+static int infl_prepare(const HandleScope& hs, int64_t rows, int64_t n, bool need_g, bool need_contrib, bool need_z) {
+  cf_handle* const h = hs.h;
   const size_t bytes = (size_t)rows * (size_t)n * 8;
   DevBuf* const buf[3] = {&h->i_g, &h->i_contrib, &h->i_z};
   const bool need[3] = {need_g, need_contrib, need_z};
@@ -3165,16 +3104,17 @@ static int infl_prepare(cf_handle* h, int64_t rows, int64_t n, bool need_g, bool
   return 0;
 }
 
-// Arguments checked, h->mu held, the handle's device current.  Device pointers throughout.
-static int infl_run(cf_handle* h, const cf_prec* prec, const double* d_theta, int64_t S, const double* d_w, int32_t block,
+// Arguments checked.  Device pointers throughout.
+static int infl_run(const HandleScope& hs, const cf_prec* prec, const double* d_theta, int64_t S, const double* d_w, int32_t block,
                     const double* thresholds, int32_t n_thr, const cf_infl_out& out, const cf_resid_acc* acc_z,
                     const cf_resid_acc* acc_contrib, hipStream_t st) {
+  cf_handle* const h = hs.h;
   int rc;
   const int64_t chunk = std::min<int64_t>(S, h->infl_chunk > 0 ? h->infl_chunk : CF_INFL_CHUNK);
   if ((rc = ensure_workspace(h, chunk))) return rc;
-  if ((rc = resid_prepare(h, chunk))) return rc;
+  if ((rc = resid_prepare(hs, chunk))) return rc;
   const int64_t n = prec->n;
-  if ((rc = infl_prepare(h, chunk, n, !out.g, acc_contrib && !out.contrib, acc_z && !out.z))) return rc;
+  if ((rc = infl_prepare(hs, chunk, n, !out.g, acc_contrib && !out.contrib, acc_z && !out.z))) return rc;
   const cf_dev_desc& d = h->d;
   const cf_infl_src src = block == CF_RB_SN
                               ? cf_infl_src{h->delta.as<const double>(), nullptr, (int64_t)d.n_ld, (int32_t)d.n_sn, 0}
@@ -3221,47 +3161,11 @@ extern "C" int cf_infl_device(cf_handle* h, cf_prec* prec, const double* d_theta
   int rc = infl_check(h, prec, d_theta, S, block, thresholds, n_thr, out, acc_z, acc_contrib);
   if (rc) return rc;
   if (S == 0) return CF_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
-  return infl_run(h, prec, d_theta, S, d_w, block, thresholds, n_thr, out ? *out : cf_infl_out{}, acc_z, acc_contrib,
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  return infl_run(hs, prec, d_theta, S, d_w, block, thresholds, n_thr, out ? *out : cf_infl_out{}, acc_z, acc_contrib,
                   (hipStream_t)hip_stream);
 }
-
-// The device twin of a host cf_resid_acc: up once, continued piece by piece on the device, down at the end.
-struct InflHostAcc {
-  DevBuf w, mean, m2, ex, used, skip;
-  cf_resid_acc dev{};
-  cf_resid_acc* host = nullptr;
-  int up(cf_resid_acc* acc, hipStream_t st) {
-    host = acc;
-    if (!acc) return 0;
-    const size_t nb = (size_t)acc->n * 8, ne = nb * (size_t)acc->n_thr;
-    dev = *acc;
-    if (w.ensure(nb) || mean.ensure(nb) || m2.ensure(nb) || used.ensure(nb) || skip.ensure(nb) || (ne && ex.ensure(ne))) return CF_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(w.p, acc->w_sum, nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(mean.p, acc->mean, nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m2.p, acc->m2, nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(used.p, acc->n_used, nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(skip.p, acc->n_skipped, nb, hipMemcpyHostToDevice, st));
-    if (ne) HIP_TRY(hipMemcpyAsync(ex.p, acc->exceed, ne, hipMemcpyHostToDevice, st));
-    dev.w_sum = w.as<double>(); dev.mean = mean.as<double>(); dev.m2 = m2.as<double>(); dev.exceed = ex.as<double>();
-    dev.n_used = used.as<int64_t>(); dev.n_skipped = skip.as<int64_t>();
-    return 0;
-  }
-  int down() {
-    if (!host) return 0;
-    const size_t nb = (size_t)host->n * 8, ne = nb * (size_t)host->n_thr;
-    HIP_TRY(hipMemcpy(host->w_sum, w.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(host->mean, mean.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(host->m2, m2.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(host->n_used, used.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(host->n_skipped, skip.p, nb, hipMemcpyDeviceToHost));
-    if (ne) HIP_TRY(hipMemcpy(host->exceed, ex.p, ne, hipMemcpyDeviceToHost));
-    return 0;
-  }
-  const cf_resid_acc* ptr() const { return host ? &dev : nullptr; }
-};
 
 // Host-buffer twin: rows in pieces through temporary device buffers on the handle's own stream (a piece is a chunk: the row
 // arrays are [piece][n]).
@@ -3272,39 +3176,23 @@ extern "C" int cf_infl(cf_handle* h, cf_prec* prec, const double* theta, int64_t
   int rc = infl_check(h, prec, theta, S, block, thresholds, n_thr, out, acc_z, acc_contrib);
   if (rc) return rc;
   if (S == 0) return CF_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceScope on_device(h->device);
-  HIP_TRY(on_device.err);
-  const int64_t piece = std::min<int64_t>(S, CF_INFL_HOST_PIECE), n = prec->n;
-  const int ndim = h->d.ndim;
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  const size_t row = (size_t)prec->n * 8;
   const cf_infl_out ho = out ? *out : cf_infl_out{};
-  double* const host_rows[4] = {ho.g, ho.contrib, ho.z, ho.loo};
-  DevBuf dth, dw, drows[4], dsample;
-  InflHostAcc az, ac;
-  if (dth.ensure((size_t)piece * ndim * 8)) return CF_ERR_HIP;
-  if (w && dw.ensure((size_t)piece * 8)) return CF_ERR_HIP;
-  for (int k = 0; k < 4; ++k)
-    if (host_rows[k] && drows[k].ensure((size_t)piece * n * 8)) return CF_ERR_HIP;
-  if (ho.sample && dsample.ensure((size_t)piece * CF_INFL_NCOL * 8)) return CF_ERR_HIP;
-  if ((rc = az.up(acc_z, h->stream)) || (rc = ac.up(acc_contrib, h->stream))) return rc;
+  RowStage rows(h->stream, std::min<int64_t>(S, CF_INFL_HOST_PIECE));
+  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
+  const double* dw = rows.in(w, 8);
   cf_infl_out dout{};
   dout.struct_size = (int32_t)sizeof(cf_infl_out);
-  dout.g = drows[0].as<double>(); dout.contrib = drows[1].as<double>(); dout.z = drows[2].as<double>(); dout.loo = drows[3].as<double>();
-  dout.sample = dsample.as<double>();
-  for (int64_t s0 = 0; s0 < S; s0 += piece) {
-    const int64_t m = std::min(piece, S - s0);
-    HIP_TRY(hipMemcpyAsync(dth.p, theta + s0 * ndim, (size_t)m * ndim * 8, hipMemcpyHostToDevice, h->stream));
-    if (w) HIP_TRY(hipMemcpyAsync(dw.p, w + s0, (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
-    if ((rc = infl_run(h, prec, dth.as<const double>(), m, w ? dw.as<const double>() : nullptr, block, thresholds, n_thr, dout,
-                       az.ptr(), ac.ptr(), h->stream)))
-      return rc;
-    for (int k = 0; k < 4; ++k)
-      if (host_rows[k])
-        HIP_TRY(hipMemcpyAsync(host_rows[k] + s0 * n, drows[k].p, (size_t)m * n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (ho.sample)
-      HIP_TRY(hipMemcpyAsync(ho.sample + s0 * CF_INFL_NCOL, dsample.p, (size_t)m * CF_INFL_NCOL * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
+  dout.g = rows.out(ho.g, row); dout.contrib = rows.out(ho.contrib, row); dout.z = rows.out(ho.z, row); dout.loo = rows.out(ho.loo, row);
+  dout.sample = rows.out(ho.sample, (size_t)CF_INFL_NCOL * 8);
+  HostAccTwin az, ac;
+  if ((rc = az.up(acc_z, h->stream)) || (rc = ac.up(acc_contrib, h->stream))) return rc;
+  if ((rc = rows.run(S, [&](int64_t, int64_t m) {
+         return infl_run(hs, prec, dth, m, dw, block, thresholds, n_thr, dout, az.ptr(), ac.ptr(), h->stream);
+       })))
+    return rc;
   if ((rc = az.down()) || (rc = ac.down())) return rc;
   return CF_OK;
 }

@@ -41,9 +41,8 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
+#include "cf_host.h"
 #include "cf_rng.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
 #define CF_BRIDGE_ROW_THREADS 256
 #define CF_BRIDGE_BATCH 16  // iterations enqueued between two host reads of the done flag
@@ -325,7 +324,7 @@ extern "C" int cf_bridge_forward(const double* d_theta, int64_t n, int32_t ndim,
   hipStream_t st = (hipStream_t)hip_stream;
   const dim3 grid((unsigned)((n + CF_BRIDGE_ROW_THREADS - 1) / CF_BRIDGE_ROW_THREADS));
   CF_BRIDGE_DISPATCH(bridge_forward_kernel, d_theta, n, g, d_z, d_log_jac)
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_bridge_forward: launch failed");
+  return cf_launch_status("cf_bridge_forward");
 }
 
 extern "C" int cf_bridge_points(const double* d_z, int64_t n, int32_t ndim, const double* lo, const double* hi, const double* mean,
@@ -337,7 +336,7 @@ extern "C" int cf_bridge_points(const double* d_z, int64_t n, int32_t ndim, cons
   hipStream_t st = (hipStream_t)hip_stream;
   const dim3 grid((unsigned)((n + CF_BRIDGE_ROW_THREADS - 1) / CF_BRIDGE_ROW_THREADS));
   CF_BRIDGE_DISPATCH(bridge_points_kernel, d_z, n, g, (int)mirror, d_theta, d_log_jac)
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_bridge_points: launch failed");
+  return cf_launch_status("cf_bridge_points");
 }
 
 extern "C" int cf_bridge_draw(uint64_t key, int64_t first, int64_t n, int32_t ndim, double* d_z, void* hip_stream) {
@@ -349,7 +348,7 @@ extern "C" int cf_bridge_draw(uint64_t key, int64_t first, int64_t n, int32_t nd
   if (blocks > (int64_t)INT32_MAX) return cf_set_error(CF_ERR_INVALID, "cf_bridge_draw: too many draws for one call");
   hipLaunchKernelGGL(bridge_draw_kernel, dim3((unsigned)blocks), dim3(CF_BRIDGE_ROW_THREADS), 0, (hipStream_t)hip_stream, key, first,
                      n, (int)ndim, d_z);
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_bridge_draw: launch failed");
+  return cf_launch_status("cf_bridge_draw");
 }
 
 extern "C" int cf_bridge_solve(const double* d_l1, int64_t n1, const double* d_l2, int64_t n2, double lstar, double s1, double s2,

@@ -13,8 +13,7 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
+#include "cf_host.h"
 
 #define CF_CHAIN_SEGS 8  // time segments (one wave each) per workgroup of 64 series
 #define CF_CHAIN_R 16    // lags held in registers per pass over a segment
@@ -121,7 +120,7 @@ extern "C" int cf_chain_mean(const double* d_x, int64_t n_t, int64_t n_s, double
   if (n_t < 1 || n_s < 1 || (n_s + 63) / 64 > INT32_MAX) return cf_set_error(CF_ERR_INVALID, "cf_chain_mean: bad chain shape");
   hipLaunchKernelGGL(chain_mean_kernel, dim3(chain_blocks(n_s)), dim3(64 * CF_CHAIN_SEGS), 0, (hipStream_t)hip_stream, d_x, n_t, n_s,
                      d_mean);
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_chain_mean: launch failed");
+  return cf_launch_status("cf_chain_mean");
 }
 
 extern "C" int cf_chain_lagsum(const double* d_x, const double* d_mean, int64_t n_t, int64_t n_s, int64_t lag0, int32_t nlag,
@@ -131,7 +130,7 @@ extern "C" int cf_chain_lagsum(const double* d_x, const double* d_mean, int64_t 
   if (lag0 < 0 || nlag < 1) return cf_set_error(CF_ERR_INVALID, "cf_chain_lagsum: need lag0 >= 0 and nlag >= 1");
   hipLaunchKernelGGL(chain_lagsum_kernel, dim3(chain_blocks(n_s)), dim3(64 * CF_CHAIN_SEGS), 0, (hipStream_t)hip_stream, d_x, d_mean,
                      n_t, n_s, lag0, (int)nlag, d_out);
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_chain_lagsum: launch failed");
+  return cf_launch_status("cf_chain_lagsum");
 }
 
 extern "C" int cf_chain_acf_mean(const double* d_lagsum, const double* d_c0, int64_t n_w, int32_t ndim, int32_t nlag, double* d_f,
@@ -141,5 +140,5 @@ extern "C" int cf_chain_acf_mean(const double* d_lagsum, const double* d_c0, int
   const int64_t n = (int64_t)nlag * ndim;
   hipLaunchKernelGGL(chain_acf_mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, d_lagsum, d_c0,
                      n_w, (int)ndim, (int)nlag, d_f);
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_chain_acf_mean: launch failed");
+  return cf_launch_status("cf_chain_acf_mean");
 }

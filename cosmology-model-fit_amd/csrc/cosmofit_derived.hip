@@ -33,9 +33,8 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
+#include "cf_host.h"
 #include "cosmofit_device.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
@@ -385,9 +384,7 @@ int cf_derived_launch(const cf_dev_desc& d, const cf_derived_kargs& a, const dou
                       hipStream_t st) {
   const int64_t blocks = (S + DQ_TPB - 1) / DQ_TPB;
   hipLaunchKernelGGL(derived_kernel, dim3((unsigned)blocks), dim3(DQ_TPB), 0, st, d, a, d_theta, S, d_out);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string("cf_derived_device: ") + hipGetErrorString(err));
-  return CF_OK;
+  return cf_launch_status("cf_derived_device");
 }
 
 int cf_curves_launch(const cf_dev_desc& d, const double* d_theta, int64_t S, int code, const double* d_z, int nz, double* d_out,
@@ -409,7 +406,5 @@ int cf_curves_launch(const cf_dev_desc& d, const double* d_theta, int64_t S, int
     }
   }
   hipLaunchKernelGGL(curves_kernel, dim3((unsigned)S), dim3(DQ_TPB), lds, st, d, d_theta, S, code, chs, d_z, nz, d_out);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string("cf_curves_device: ") + hipGetErrorString(err));
-  return CF_OK;
+  return cf_launch_status("cf_curves_device");
 }

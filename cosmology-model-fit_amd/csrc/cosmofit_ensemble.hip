@@ -16,11 +16,11 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
+#include "cf_host.h"
 #include "cf_rng.h"
 
 #define CF_ENS_MAX_NDIM 16
 
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
 // ens_mix / ens_uniform / ens_normal: cf_rng.h (shared with cosmofit_mock.hip)
 
@@ -484,7 +484,7 @@ extern "C" int cf_ens_kde_prepare(const double* d_all_pos, int64_t w_total, int3
     return cf_set_error(CF_ERR_INVALID, "cf_ens_kde_prepare: the KDE move needs more than ndim walkers in the complementary set");
   hipLaunchKernelGGL(ens_kde_prepare_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, d_all_pos, nc, (int)ndim, (int)n_splits,
                      (int)split, split_key, d_params, d_wc);
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_ens_kde_prepare: launch failed");
+  return cf_launch_status("cf_ens_kde_prepare");
 }
 
 extern "C" int cf_ens_propose(int32_t kind, const double* d_all_pos, int64_t w_total, int32_t ndim, int32_t n_splits, int32_t split,
@@ -504,7 +504,7 @@ extern "C" int cf_ens_propose(int32_t kind, const double* d_all_pos, int64_t w_t
   if (kind == 2)
     hipLaunchKernelGGL(ens_kde_logfactor_kernel, dim3((unsigned)n_active), dim3(256), 0, (hipStream_t)hip_stream,
                        d_all_pos, nc, (int)ndim, d_ids, n_active, d_kde_params, d_kde_wc, (const double*)d_y, d_log_factor);
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_ens_propose: launch failed");
+  return cf_launch_status("cf_ens_propose");
 }
 
 extern "C" int cf_ens_accept(const int64_t* d_ids, const int64_t* d_local_idx, int64_t n_active, int32_t ndim, uint64_t key0,
@@ -517,7 +517,7 @@ extern "C" int cf_ens_accept(const int64_t* d_ids, const int64_t* d_local_idx, i
   hipLaunchKernelGGL(ens_accept_kernel, dim3((unsigned)((n_active + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, d_ids,
                      d_local_idx, n_active, (int)ndim, key0, d_y, d_lp_new, d_log_factor, d_x_local, d_logp_local,
                      (unsigned long long*)d_n_accepted, (double*)nullptr, (double*)nullptr, (long long*)nullptr);
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_ens_accept: launch failed");
+  return cf_launch_status("cf_ens_accept");
 }
 
 extern "C" int cf_ens_accept_record(const int64_t* d_ids, const int64_t* d_local_idx, int64_t n_active, int32_t ndim, uint64_t key0,
@@ -533,7 +533,7 @@ extern "C" int cf_ens_accept_record(const int64_t* d_ids, const int64_t* d_local
   hipLaunchKernelGGL(ens_accept_kernel, dim3((unsigned)((n_active + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, d_ids,
                      d_local_idx, n_active, (int)ndim, key0, d_y, d_lp_new, d_log_factor, d_x_local, d_logp_local,
                      (unsigned long long*)d_n_accepted, d_chain_slot, d_logp_slot, (long long*)d_walker_accepted);
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_ens_accept_record: launch failed");
+  return cf_launch_status("cf_ens_accept_record");
 }
 
 extern "C" int cf_ens_active_set(uint64_t split_key, int32_t n_splits, int32_t split, int64_t shard_start, int64_t shard_stop,
@@ -546,5 +546,5 @@ extern "C" int cf_ens_active_set(uint64_t split_key, int32_t n_splits, int32_t s
   const int64_t n_groups = (shard_stop - 1) / n_splits - shard_start / n_splits + 1;
   hipLaunchKernelGGL(ens_active_set_kernel, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, split_key,
                      (int)n_splits, (int)split, shard_start, shard_stop, d_ids, d_local_idx);
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_ens_active_set: launch failed");
+  return cf_launch_status("cf_ens_active_set");
 }

@@ -31,9 +31,8 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
+#include "cf_host.h"
 #include "cf_wave_scan.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
@@ -386,13 +385,6 @@ field_kernel(fd_desc d, const double* __restrict__ theta, int64_t S, fd_args q) 
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-struct FdBuf {
-  void* p = nullptr;
-  ~FdBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8) == hipSuccess ? 0 : 1; }
-  template <class T> T* as() const { return (T*)p; }
-};
-
 int fd_fail(const char* fn, const std::string& msg) { return cf_set_error(CF_ERR_INVALID, std::string(fn) + ": " + msg); }
 
 // everything that can be refused without a device; fills the kernel's descriptor
@@ -496,8 +488,7 @@ int fd_launch(const char* fn, const fd_desc& d, const double* d_theta, int64_t S
     if (d.fde == CF_FDE_THAWING) hipLaunchKernelGGL(field_kernel<CF_FDE_THAWING>, grid, block, lds, st, d, th, m, b);
     else if (d.fde == CF_FDE_WCDM) hipLaunchKernelGGL(field_kernel<CF_FDE_WCDM>, grid, block, lds, st, d, th, m, b);
     else hipLaunchKernelGGL(field_kernel<CF_FDE_CPL>, grid, block, lds, st, d, th, m, b);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(err));
+    if (int rc = cf_launch_status(fn)) return rc;
   }
   return CF_OK;
 }
@@ -526,12 +517,6 @@ extern "C" int cf_field_device(const cf_field_desc* desc, const double* d_theta,
 
 #define FD_HOST_POINTS (1 << 22)  // rows x points per pass of cf_field and per output: 32 MB of device buffer each
 
-#define FD_HIP(expr)                                                                                                   \
-  do {                                                                                                                 \
-    const hipError_t e_ = (expr);                                                                                      \
-    if (e_ != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string("cf_field: " #expr ": ") + hipGetErrorString(e_)); \
-  } while (0)
-
 extern "C" int cf_field(const cf_field_desc* desc, const double* theta, int64_t S, const cf_field_queries* queries,
                         const cf_field_out* out) {
   fd_desc d;
@@ -544,59 +529,36 @@ extern "C" int cf_field(const cf_field_desc* desc, const double* theta, int64_t 
     return cf_set_error(CF_ERR_NO_DEVICE, "cf_field: no HIP device visible (this library has no CPU path)");
   const cf_field_queries& q = *queries;
   const int64_t widest = std::max(1, std::max(q.n_aq, std::max(q.n_phi, q.n_t)));
-  const int64_t chunk = std::min<int64_t>(S, FD_HOST_POINTS / widest);
-  // the eleven per-point outputs with their widths, then scalars and status
-  double* const host[11] = {out->phi_a, out->t_a, out->w_a, out->K_a, out->V_a, out->phi_grid, out->a_phi, out->V_phi,
-                            out->t_grid, out->a_t, out->phi_t};
-  const int width[11] = {q.n_aq, q.n_aq, q.n_aq, q.n_aq, q.n_aq, q.n_phi, q.n_phi, q.n_phi, q.n_t, q.n_t, q.n_t};
-  FdBuf dth, daq, dphiq, dtq, dsc, dst, dev[11];
-  if (dth.alloc((size_t)chunk * d.ndim * 8)) return cf_set_error(CF_ERR_HIP, "cf_field: hipMalloc failed");
+  // the null stream, as the caller of cf_field_device without a stream of its own
+  RowStage rows((hipStream_t)0, std::min<int64_t>(S, FD_HOST_POINTS / widest));
+  const double* dth = rows.in(theta, (size_t)d.ndim * 8);
+  // the query points go up once; fd_validate has refused a non-null set without points and an output without its set, so
+  // no buffer here or below has zero bytes
+  DevBuf daq, dphiq, dtq;
   cf_field_queries dq = q;
   if (q.a_q) {
-    if (daq.alloc((size_t)q.n_aq * 8)) return cf_set_error(CF_ERR_HIP, "cf_field: hipMalloc failed");
-    FD_HIP(hipMemcpy(daq.p, q.a_q, (size_t)q.n_aq * 8, hipMemcpyHostToDevice));
+    if (daq.ensure((size_t)q.n_aq * 8)) return CF_ERR_HIP;
+    HIP_TRY(hipMemcpy(daq.p, q.a_q, (size_t)q.n_aq * 8, hipMemcpyHostToDevice));
     dq.a_q = daq.as<const double>();
   }
   if (q.phi_q) {
-    if (dphiq.alloc((size_t)q.n_phi * 8)) return cf_set_error(CF_ERR_HIP, "cf_field: hipMalloc failed");
-    FD_HIP(hipMemcpy(dphiq.p, q.phi_q, (size_t)q.n_phi * 8, hipMemcpyHostToDevice));
+    if (dphiq.ensure((size_t)q.n_phi * 8)) return CF_ERR_HIP;
+    HIP_TRY(hipMemcpy(dphiq.p, q.phi_q, (size_t)q.n_phi * 8, hipMemcpyHostToDevice));
     dq.phi_q = dphiq.as<const double>();
   }
   if (q.t_q) {
-    if (dtq.alloc((size_t)q.n_t * 8)) return cf_set_error(CF_ERR_HIP, "cf_field: hipMalloc failed");
-    FD_HIP(hipMemcpy(dtq.p, q.t_q, (size_t)q.n_t * 8, hipMemcpyHostToDevice));
+    if (dtq.ensure((size_t)q.n_t * 8)) return CF_ERR_HIP;
+    HIP_TRY(hipMemcpy(dtq.p, q.t_q, (size_t)q.n_t * 8, hipMemcpyHostToDevice));
     dq.t_q = dtq.as<const double>();
   }
+  const size_t wa = (size_t)q.n_aq * 8, wp = (size_t)q.n_phi * 8, wt = (size_t)q.n_t * 8;
   cf_field_out dout;
-  double** const slot[11] = {&dout.phi_a, &dout.t_a, &dout.w_a, &dout.K_a, &dout.V_a, &dout.phi_grid, &dout.a_phi, &dout.V_phi,
-                             &dout.t_grid, &dout.a_t, &dout.phi_t};
-  for (int k = 0; k < 11; ++k) {
-    *slot[k] = nullptr;
-    if (!host[k]) continue;
-    if (dev[k].alloc((size_t)chunk * width[k] * 8)) return cf_set_error(CF_ERR_HIP, "cf_field: hipMalloc failed");
-    *slot[k] = dev[k].as<double>();
-  }
-  dout.scalars = nullptr;
-  dout.status = nullptr;
-  if (out->scalars) {
-    if (dsc.alloc((size_t)chunk * CF_FIELD_NSCALAR * 8)) return cf_set_error(CF_ERR_HIP, "cf_field: hipMalloc failed");
-    dout.scalars = dsc.as<double>();
-  }
-  if (out->status) {
-    if (dst.alloc((size_t)chunk * 4)) return cf_set_error(CF_ERR_HIP, "cf_field: hipMalloc failed");
-    dout.status = dst.as<int32_t>();
-  }
+  dout.phi_a = rows.out(out->phi_a, wa); dout.t_a = rows.out(out->t_a, wa); dout.w_a = rows.out(out->w_a, wa);
+  dout.K_a = rows.out(out->K_a, wa); dout.V_a = rows.out(out->V_a, wa);
+  dout.phi_grid = rows.out(out->phi_grid, wp); dout.a_phi = rows.out(out->a_phi, wp); dout.V_phi = rows.out(out->V_phi, wp);
+  dout.t_grid = rows.out(out->t_grid, wt); dout.a_t = rows.out(out->a_t, wt); dout.phi_t = rows.out(out->phi_t, wt);
+  dout.scalars = rows.out(out->scalars, (size_t)CF_FIELD_NSCALAR * 8);
+  dout.status = rows.out(out->status, 4);
   const fd_args a = fd_pack(&dq, &dout);
-  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-    const int64_t m = std::min(chunk, S - s0);
-    FD_HIP(hipMemcpy(dth.p, theta + s0 * d.ndim, (size_t)m * d.ndim * 8, hipMemcpyHostToDevice));
-    const int rc = fd_launch("cf_field", d, dth.as<const double>(), m, a, (hipStream_t)0);
-    if (rc) return rc;
-    FD_HIP(hipDeviceSynchronize());
-    for (int k = 0; k < 11; ++k)
-      if (host[k]) FD_HIP(hipMemcpy(host[k] + s0 * width[k], dev[k].p, (size_t)m * width[k] * 8, hipMemcpyDeviceToHost));
-    if (out->scalars) FD_HIP(hipMemcpy(out->scalars + s0 * CF_FIELD_NSCALAR, dsc.p, (size_t)m * CF_FIELD_NSCALAR * 8, hipMemcpyDeviceToHost));
-    if (out->status) FD_HIP(hipMemcpy(out->status + s0, dst.p, (size_t)m * 4, hipMemcpyDeviceToHost));
-  }
-  return CF_OK;
+  return rows.run(S, [&](int64_t, int64_t m) { return fd_launch("cf_field", d, dth, m, a, (hipStream_t)0); });
 }

@@ -40,20 +40,13 @@
 #include <vector>
 
 #include "../../include/cosmofit.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
+#include "cf_host.h"
 
 #define GP_WAVE 64
 #define GP_PRED_TPB 256
 #define GP_HOST_CHUNK 16384
 #define GP_MAX_ROWS (((int64_t)1 << 31) - 1)
 #define GP_LAUNCH_ROWS ((int64_t)1 << 22)  // rows (workgroups) per grid: 2^30 threads at 256 per workgroup
-
-#define GP_TRY(expr)                                                                                     \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 struct GpDev {
   const double* z;  // [n]
@@ -67,7 +60,7 @@ struct GpDev {
 struct cf_gp {
   int device = 0;
   GpDev d{};
-  void* buf = nullptr;  // z, y, C, then the counter
+  DevBuf buf;  // z, y, C, then the counter
   hipStream_t stream = nullptr;
   std::mutex mu;
 };
@@ -281,8 +274,7 @@ static int gp_launch_mll(cf_gp* gp, const double* d_theta, int64_t W, double* d_
     const int64_t m = std::min<int64_t>(GP_LAUNCH_ROWS, W - r0);
     hipLaunchKernelGGL(gp_mll_kernel, dim3((unsigned)m), dim3(GP_WAVE), lds, st, gp->d, d_theta + r0 * CF_GP_NDIM, m, d_out + r0,
                        d_parts ? d_parts + 2 * r0 : nullptr);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string("cf_gp_mll_device: ") + hipGetErrorString(err));
+    if (int rc = cf_launch_status("cf_gp_mll_device")) return rc;
   }
   return CF_OK;
 }
@@ -294,39 +286,10 @@ static int gp_launch_predict(cf_gp* gp, const double* d_theta, int64_t S, const 
     const int64_t m = std::min<int64_t>(GP_LAUNCH_ROWS, S - r0);
     hipLaunchKernelGGL(gp_predict_kernel, dim3((unsigned)m), dim3(GP_PRED_TPB), lds, st, gp->d, d_theta + r0 * CF_GP_NDIM, m, d_z, nz,
                        noise, d_out + r0 * (int64_t)nz * 5);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string("cf_gp_predict_device: ") + hipGetErrorString(err));
+    if (int rc = cf_launch_status("cf_gp_predict_device")) return rc;
   }
   return CF_OK;
 }
-
-struct GpDeviceScope {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit GpDeviceScope(int dev) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    if (cur != dev) {
-      err = hipSetDevice(dev);
-      if (err == hipSuccess) prev = cur;
-    }
-  }
-  ~GpDeviceScope() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  GpDeviceScope(const GpDeviceScope&) = delete;
-  GpDeviceScope& operator=(const GpDeviceScope&) = delete;
-};
-
-struct GpBuf {
-  void* p = nullptr;
-  ~GpBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) {
-    GP_TRY(hipMalloc(&p, bytes));
-    return 0;
-  }
-  template <class T> T* as() const { return (T*)p; }
-};
 
 static bool gp_all_finite(const double* a, int64_t n) {
   for (int64_t k = 0; k < n; ++k)
@@ -371,19 +334,19 @@ extern "C" int cf_gp_create(const cf_gp_desc* c, cf_gp** out) {
   cf_gp* gp = new cf_gp();
   gp->device = c->device;
   auto bail = [&](int code) { cf_gp_destroy(gp); return code; };
-  GpDeviceScope on_device(gp->device);
+  DeviceScope on_device(gp->device);
   if (on_device.err != hipSuccess) return bail(cf_set_error(CF_ERR_HIP, "cf_gp_create: hipSetDevice failed"));
   const size_t nd = (size_t)2 * n + (size_t)n * n;
-  if (hipMalloc(&gp->buf, (nd + 1) * 8) != hipSuccess) return bail(cf_set_error(CF_ERR_HIP, "cf_gp_create: hipMalloc failed"));
+  if (gp->buf.ensure((nd + 1) * 8)) return bail(cf_set_error(CF_ERR_HIP, "cf_gp_create: hipMalloc failed"));
   std::vector<double> host(nd + 1, 0.0);
   std::copy(c->z, c->z + n, host.begin());
   std::copy(c->y, c->y + n, host.begin() + n);
   std::copy(c->cov, c->cov + (size_t)n * n, host.begin() + 2 * n);
-  if (hipMemcpy(gp->buf, host.data(), (nd + 1) * 8, hipMemcpyHostToDevice) != hipSuccess)
+  if (hipMemcpy(gp->buf.p, host.data(), (nd + 1) * 8, hipMemcpyHostToDevice) != hipSuccess)
     return bail(cf_set_error(CF_ERR_HIP, "cf_gp_create: hipMemcpy failed"));
   if (hipStreamCreateWithFlags(&gp->stream, hipStreamNonBlocking) != hipSuccess)
     return bail(cf_set_error(CF_ERR_HIP, "cf_gp_create: hipStreamCreate failed"));
-  double* base = (double*)gp->buf;
+  double* base = gp->buf.as<double>();
   gp->d.z = base;
   gp->d.y = base + n;
   gp->d.C = base + 2 * n;
@@ -400,25 +363,22 @@ extern "C" int cf_gp_create(const cf_gp_desc* c, cf_gp** out) {
 
 extern "C" void cf_gp_destroy(cf_gp* gp) {
   if (!gp) return;
-  {
-    GpDeviceScope on_device(gp->device);
-    if (gp->stream) {
-      (void)hipStreamSynchronize(gp->stream);
-      (void)hipStreamDestroy(gp->stream);
-    }
-    if (gp->buf) (void)hipFree(gp->buf);
+  DeviceScope on_device(gp->device);
+  if (gp->stream) {
+    (void)hipStreamSynchronize(gp->stream);
+    (void)hipStreamDestroy(gp->stream);
   }
-  delete gp;
+  delete gp;  // frees buf
 }
 
 extern "C" int cf_gp_get_info(cf_gp* gp, cf_gp_info* info) {
   if (!gp || !info) return cf_set_error(CF_ERR_INVALID, "cf_gp_get_info: null argument");
   std::lock_guard<std::mutex> lk(gp->mu);
-  GpDeviceScope on_device(gp->device);
-  GP_TRY(on_device.err);
+  DeviceScope on_device(gp->device);
+  HIP_TRY(on_device.err);
   unsigned long long cnt = 0;
-  GP_TRY(hipDeviceSynchronize());
-  GP_TRY(hipMemcpy(&cnt, gp->d.fail_count, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(&cnt, gp->d.fail_count, 8, hipMemcpyDeviceToHost));
   info->n = gp->d.n;
   info->device = gp->device;
   info->ld = gp->d.ld;
@@ -445,8 +405,8 @@ extern "C" int cf_gp_mll_device(cf_gp* gp, const double* d_theta, int64_t W, dou
   if (rc) return rc;
   if (W == 0) return CF_OK;
   if (!d_theta || !d_out) return cf_set_error(CF_ERR_INVALID, "cf_gp_mll_device: null argument");
-  GpDeviceScope on_device(gp->device);
-  GP_TRY(on_device.err);
+  DeviceScope on_device(gp->device);
+  HIP_TRY(on_device.err);
   return gp_launch_mll(gp, d_theta, W, d_out, d_parts, (hipStream_t)hip_stream);
 }
 
@@ -457,8 +417,8 @@ extern "C" int cf_gp_predict_device(cf_gp* gp, const double* d_theta, int64_t S,
   if ((rc = gp_check_predict(nz, noise, "cf_gp_predict_device"))) return rc;
   if (S == 0) return CF_OK;
   if (!d_theta || !d_zstar || !d_out) return cf_set_error(CF_ERR_INVALID, "cf_gp_predict_device: null argument");
-  GpDeviceScope on_device(gp->device);
-  GP_TRY(on_device.err);
+  DeviceScope on_device(gp->device);
+  HIP_TRY(on_device.err);
   return gp_launch_predict(gp, d_theta, S, d_zstar, nz, noise, d_out, (hipStream_t)hip_stream);
 }
 
@@ -469,21 +429,13 @@ extern "C" int cf_gp_mll(cf_gp* gp, const double* theta, int64_t W, double* out,
   if (W == 0) return CF_OK;
   if (!theta || !out) return cf_set_error(CF_ERR_INVALID, "cf_gp_mll: null argument");
   std::lock_guard<std::mutex> lk(gp->mu);
-  GpDeviceScope on_device(gp->device);
-  GP_TRY(on_device.err);
-  const int64_t chunk = std::min<int64_t>(W, GP_HOST_CHUNK);
-  GpBuf dth, dout, dparts;
-  if (dth.alloc((size_t)chunk * CF_GP_NDIM * 8) || dout.alloc((size_t)chunk * 8) || (parts && dparts.alloc((size_t)chunk * 16)))
-    return CF_ERR_HIP;
-  for (int64_t s0 = 0; s0 < W; s0 += chunk) {
-    const int64_t m = std::min(chunk, W - s0);
-    GP_TRY(hipMemcpyAsync(dth.p, theta + s0 * CF_GP_NDIM, (size_t)m * CF_GP_NDIM * 8, hipMemcpyHostToDevice, gp->stream));
-    if ((rc = gp_launch_mll(gp, dth.as<const double>(), m, dout.as<double>(), parts ? dparts.as<double>() : nullptr, gp->stream))) return rc;
-    GP_TRY(hipMemcpyAsync(out + s0, dout.p, (size_t)m * 8, hipMemcpyDeviceToHost, gp->stream));
-    if (parts) GP_TRY(hipMemcpyAsync(parts + 2 * s0, dparts.p, (size_t)m * 16, hipMemcpyDeviceToHost, gp->stream));
-    GP_TRY(hipStreamSynchronize(gp->stream));
-  }
-  return CF_OK;
+  DeviceScope on_device(gp->device);
+  HIP_TRY(on_device.err);
+  RowStage rows(gp->stream, std::min<int64_t>(W, GP_HOST_CHUNK));
+  const double* dth = rows.in(theta, CF_GP_NDIM * 8);
+  double* dout = rows.out(out, 8);
+  double* dparts = rows.out(parts, 16);
+  return rows.run(W, [&](int64_t, int64_t m) { return gp_launch_mll(gp, dth, m, dout, dparts, gp->stream); });
 }
 
 extern "C" int cf_gp_predict(cf_gp* gp, const double* theta, int64_t S, const double* zstar, int32_t nz, double noise, double* out) {
@@ -493,19 +445,16 @@ extern "C" int cf_gp_predict(cf_gp* gp, const double* theta, int64_t S, const do
   if (S == 0) return CF_OK;
   if (!theta || !zstar || !out) return cf_set_error(CF_ERR_INVALID, "cf_gp_predict: null argument");
   std::lock_guard<std::mutex> lk(gp->mu);
-  GpDeviceScope on_device(gp->device);
-  GP_TRY(on_device.err);
+  DeviceScope on_device(gp->device);
+  HIP_TRY(on_device.err);
   const int64_t per_row = (int64_t)nz * 5;
-  const int64_t chunk = std::min<int64_t>(S, std::max<int64_t>(1, ((int64_t)GP_HOST_CHUNK * 256) / per_row));
-  GpBuf dth, dz, dout;
-  if (dth.alloc((size_t)chunk * CF_GP_NDIM * 8) || dz.alloc((size_t)nz * 8) || dout.alloc((size_t)chunk * per_row * 8)) return CF_ERR_HIP;
-  GP_TRY(hipMemcpyAsync(dz.p, zstar, (size_t)nz * 8, hipMemcpyHostToDevice, gp->stream));
-  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-    const int64_t m = std::min(chunk, S - s0);
-    GP_TRY(hipMemcpyAsync(dth.p, theta + s0 * CF_GP_NDIM, (size_t)m * CF_GP_NDIM * 8, hipMemcpyHostToDevice, gp->stream));
-    if ((rc = gp_launch_predict(gp, dth.as<const double>(), m, dz.as<const double>(), nz, noise, dout.as<double>(), gp->stream))) return rc;
-    GP_TRY(hipMemcpyAsync(out + s0 * per_row, dout.p, (size_t)m * per_row * 8, hipMemcpyDeviceToHost, gp->stream));
-    GP_TRY(hipStreamSynchronize(gp->stream));
-  }
-  return CF_OK;
+  RowStage rows(gp->stream, std::min<int64_t>(S, std::max<int64_t>(1, ((int64_t)GP_HOST_CHUNK * 256) / per_row)));
+  const double* dth = rows.in(theta, CF_GP_NDIM * 8);
+  double* dout = rows.out(out, (size_t)per_row * 8);
+  DevBuf dz;
+  if (dz.ensure((size_t)nz * 8)) return CF_ERR_HIP;
+  HIP_TRY(hipMemcpyAsync(dz.p, zstar, (size_t)nz * 8, hipMemcpyHostToDevice, gp->stream));
+  return rows.run(S, [&](int64_t, int64_t m) {
+    return gp_launch_predict(gp, dth, m, dz.as<const double>(), nz, noise, dout, gp->stream);
+  });
 }

@@ -44,9 +44,8 @@
 #include <vector>
 
 #include "../../include/cosmofit.h"
+#include "cf_host.h"
 #include "cosmofit_group.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -264,36 +263,12 @@ struct cf_group {
   int32_t n_groups = 0, max_m = 0;
   int device = 0;
   std::vector<int64_t> off, x_off;
-  void *d_ioff = nullptr, *d_xoff = nullptr, *d_idx = nullptr, *d_X = nullptr;
-  ~cf_group() {
-    (void)hipFree(d_ioff);
-    (void)hipFree(d_xoff);
-    (void)hipFree(d_idx);
-    (void)hipFree(d_X);
-  }
+  DevBuf d_ioff, d_xoff, d_idx, d_X;
 };
 
-#define GRP_HIP(expr)                                                                                  \
-  do {                                                                                                 \
-    const hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-  } while (0)
-
-struct GrpDevice {  // the device current while in scope
-  int prev = -1;
-  hipError_t err;
-  explicit GrpDevice(int dev) {
-    err = hipGetDevice(&prev);
-    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-  }
-  ~GrpDevice() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-static int grp_upload(void** d, const void* h, size_t bytes) {
-  GRP_HIP(hipMalloc(d, bytes));
-  GRP_HIP(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+static int grp_upload(DevBuf& d, const void* h, size_t bytes) {
+  if (d.ensure(bytes)) return CF_ERR_HIP;
+  HIP_TRY(hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice));
   return CF_OK;
 }
 
@@ -318,8 +293,8 @@ extern "C" int cf_group_create(cf_prec* prec, int32_t n_groups, const int64_t* o
     p->x_doubles += mp * mp;
     p->max_m = std::max<int32_t>(p->max_m, (int32_t)m);
   }
-  GrpDevice on_device(pv.device);
-  GRP_HIP(on_device.err);
+  DeviceScope on_device(pv.device);
+  HIP_TRY(on_device.err);
   // K is read once: the rows the groups name, copied back synchronously
   std::vector<int64_t> rowpos((size_t)pv.n, -1);
   int64_t n_rows = 0;
@@ -328,7 +303,7 @@ extern "C" int cf_group_create(cf_prec* prec, int32_t n_groups, const int64_t* o
   std::vector<double> Kh((size_t)n_rows * pv.n);
   for (int64_t i = 0; i < pv.n; ++i)
     if (rowpos[i] >= 0)
-      GRP_HIP(hipMemcpy(&Kh[(size_t)rowpos[i] * pv.n], pv.d_K + i * pv.kp, (size_t)pv.n * 8, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&Kh[(size_t)rowpos[i] * pv.n], pv.d_K + i * pv.kp, (size_t)pv.n * 8, hipMemcpyDeviceToHost));
   std::vector<double> X((size_t)p->x_doubles, 0.0);
   std::vector<int> bad_col((size_t)n_groups, -1);
   unsigned nt = std::thread::hardware_concurrency();
@@ -355,17 +330,17 @@ extern "C" int cf_group_create(cf_prec* prec, int32_t n_groups, const int64_t* o
   for (int32_t b = 0; b < n_groups; ++b)
     if (bad_col[b] >= 0)
       return cf_set_error(CF_ERR_INVALID, F + grp_name(b) + ": non-positive pivot at column " + std::to_string(bad_col[b]));
-  if ((rc = grp_upload(&p->d_ioff, p->off.data(), p->off.size() * 8))) return rc;
-  if ((rc = grp_upload(&p->d_xoff, p->x_off.data(), p->x_off.size() * 8))) return rc;
-  if ((rc = grp_upload(&p->d_idx, idx, (size_t)p->n_idx * 4))) return rc;
-  if ((rc = grp_upload(&p->d_X, X.data(), X.size() * 8))) return rc;
+  if ((rc = grp_upload(p->d_ioff, p->off.data(), p->off.size() * 8))) return rc;
+  if ((rc = grp_upload(p->d_xoff, p->x_off.data(), p->x_off.size() * 8))) return rc;
+  if ((rc = grp_upload(p->d_idx, idx, (size_t)p->n_idx * 4))) return rc;
+  if ((rc = grp_upload(p->d_X, X.data(), X.size() * 8))) return rc;
   *out = p.release();
   return CF_OK;
 }
 
 extern "C" void cf_group_destroy(cf_group* p) {
   if (!p) return;
-  GrpDevice on_device(p->device);
+  DeviceScope on_device(p->device);
   delete p;
 }
 
@@ -400,13 +375,13 @@ extern "C" int cf_group_quad_device(cf_group* p, const double* d_g, int64_t g_pi
   if (!p) return cf_set_error(CF_ERR_INVALID, "cf_group_quad_device: null cf_group");
   int rc = cf_group_quad_check_args(p->n, p->n_groups, d_g, g_pitch, S, d_q, q_pitch);
   if (rc || S == 0) return rc;
-  GrpDevice on_device(p->device);
-  GRP_HIP(on_device.err);
-  const cf_group_dev gd{(const int64_t*)p->d_ioff, (const int64_t*)p->d_xoff, (const int32_t*)p->d_idx, (const double*)p->d_X};
+  DeviceScope on_device(p->device);
+  HIP_TRY(on_device.err);
+  const cf_group_dev gd{p->d_ioff.as<const int64_t>(), p->d_xoff.as<const int64_t>(), p->d_idx.as<const int32_t>(),
+                        p->d_X.as<const double>()};
   const dim3 grid((unsigned)((S + GQ_BM - 1) / GQ_BM), (unsigned)p->n_groups);
   hipLaunchKernelGGL(group_quad_kernel, grid, dim3(GQ_TPB), 0, (hipStream_t)hip_stream, gd, d_g, g_pitch, S, d_q, q_pitch);
-  GRP_HIP(hipGetLastError());
-  return CF_OK;
+  return cf_launch_status("cf_group_quad_device");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -635,7 +610,7 @@ extern "C" int cf_reweight_device(const double* d_lw, int64_t lw_pitch, int64_t 
   const int64_t n_slices = (S + CF_RW_SLICE - 1) / CF_RW_SLICE;
   const int rec = CF_RW_NCOL(ncol), n_stat = rec - 1;
   double* work = nullptr;
-  GRP_HIP(hipMallocAsync(reinterpret_cast<void**>(&work), (size_t)(n_slices * G * (1 + n_stat)) * 8, st));
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&work), (size_t)(n_slices * G * (1 + n_stat)) * 8, st));
   double* part_max = work;
   double* part = work + n_slices * G;
   rw_pivot pv{};

@@ -28,9 +28,8 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
+#include "cf_host.h"
 #include "cosmofit_infl.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -180,15 +179,11 @@ int cf_prec_gemm_launch(const cf_infl_src& src, int64_t rows, const double* K, i
                         hipStream_t st) {
   const dim3 grid((unsigned)((rows + PG_BM - 1) / PG_BM), (unsigned)((src.n + PG_BN - 1) / PG_BN));
   hipLaunchKernelGGL(prec_gemm_kernel, grid, dim3(PG_TPB), 0, st, src, rows, K, kp, g, g_pitch);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string("cf_prec_apply_device: ") + hipGetErrorString(err));
-  return CF_OK;
+  return cf_launch_status("cf_prec_apply_device");
 }
 
 int cf_infl_row_launch(const cf_infl_src& src, int64_t rows, const cf_infl_rows& a, hipStream_t st) {
   hipLaunchKernelGGL(infl_row_kernel, dim3((unsigned)((rows + IR_ROWS_PER_WG - 1) / IR_ROWS_PER_WG)), dim3(IR_TPB), 0, st, src, rows,
                      a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string("cf_infl_device: ") + hipGetErrorString(err));
-  return CF_OK;
+  return cf_launch_status("cf_infl_device");
 }

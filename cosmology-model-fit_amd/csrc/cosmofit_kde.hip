@@ -40,8 +40,7 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
+#include "cf_host.h"
 
 #define CF_KDE_THREADS 256
 #define CF_KDE_QPT 2  // queries per thread: two independent exp chains per lane

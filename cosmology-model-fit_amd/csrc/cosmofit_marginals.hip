@@ -13,8 +13,7 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
+#include "cf_host.h"
 
 #define CF_MARG_THREADS 256
 #define CF_MARG_PER_THREAD 4  // consecutive values per thread of the index pass: one 4-byte store
@@ -189,7 +188,7 @@ extern "C" int cf_marg_bin(const double* d_x, int64_t n, int32_t ndim, const dou
   const size_t lds = ((size_t)ndim * (nbins + 1) + ndim) * sizeof(double);
   hipLaunchKernelGGL(marg_bin_kernel, dim3((unsigned)blocks), dim3(CF_MARG_THREADS), lds, (hipStream_t)hip_stream, d_x, total,
                      (int)ndim, (int)nbins, d_edges, d_idx, (int)(((uintptr_t)d_idx & 3) == 0));
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_marg_bin: launch failed");
+  return cf_launch_status("cf_marg_bin");
 }
 
 extern "C" int cf_marg_hist(const uint8_t* d_idx, const double* d_w, double w_max, int64_t n, int32_t ndim, int32_t nbins,
@@ -237,5 +236,5 @@ extern "C" int cf_marg_hist(const uint8_t* d_idx, const double* d_w, double w_ma
   if (npairs > 0)
     hipLaunchKernelGGL(k2, dim3((unsigned)nseg2, (unsigned)npairs), dim3(CF_MARG_THREADS), lds2, st, d_idx, d_w, w_max, two_s, n,
                        (int)ndim, (int)nbins, pr, reinterpret_cast<unsigned long long*>(d_h2));
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, "cf_marg_hist: launch failed");
+  return cf_launch_status("cf_marg_hist");
 }

@@ -23,10 +23,9 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
+#include "cf_host.h"
 #include "cf_rng.h"
 #include "cosmofit_mock.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
 #define MK_TPB 256
 #define MK_ROWS_PER_WG (MK_TPB / 64)
@@ -96,9 +95,7 @@ __global__ void __launch_bounds__(MK_TPB) mock_normals_kernel(uint64_t key, int6
 int cf_mock_launch(const cf_mock_args& a, int64_t rows, const int32_t* d_mock, double* d_out, double* d_cross, hipStream_t st) {
   hipLaunchKernelGGL(mock_shift_kernel, dim3((unsigned)((rows + MK_ROWS_PER_WG - 1) / MK_ROWS_PER_WG)), dim3(MK_TPB), 0, st, a, rows,
                      d_mock, d_out, d_cross);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string("cf_mock_eval_device: ") + hipGetErrorString(err));
-  return CF_OK;
+  return cf_launch_status("cf_mock_eval_device");
 }
 
 extern "C" int cf_mock_normals(uint64_t key, int64_t k0, int64_t K, int32_t n, double* d_out, void* hip_stream) {
@@ -110,7 +107,5 @@ extern "C" int cf_mock_normals(uint64_t key, int64_t k0, int64_t K, int32_t n, d
   const int64_t count = K * n, blocks = (count + MK_TPB - 1) / MK_TPB;
   hipLaunchKernelGGL(mock_normals_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(MK_TPB), 0, (hipStream_t)hip_stream,
                      key, k0 * n, count, d_out);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string("cf_mock_normals: ") + hipGetErrorString(err));
-  return CF_OK;
+  return cf_launch_status("cf_mock_normals");
 }

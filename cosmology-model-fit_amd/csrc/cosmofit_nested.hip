@@ -18,8 +18,7 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
+#include "cf_host.h"
 
 __device__ __forceinline__ uint64_t ns_mix(uint64_t x) {
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -160,10 +159,6 @@ static int ns_check_prior(const cf_ns_prior* p, const char* fn) {
 
 static unsigned ns_blocks(int64_t threads) { return (unsigned)((threads + 255) / 256); }
 
-static int ns_launched(const char* fn) {
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, std::string(fn) + ": launch failed");
-}
-
 extern "C" int cf_ns_prior_draw(const cf_ns_prior* prior, int64_t n, uint64_t key, double* d_u, double* d_theta, void* hip_stream) {
   int rc = ns_check_prior(prior, "cf_ns_prior_draw");
   if (rc) return rc;
@@ -171,7 +166,7 @@ extern "C" int cf_ns_prior_draw(const cf_ns_prior* prior, int64_t n, uint64_t ke
   if (n == 0) return CF_OK;
   hipLaunchKernelGGL(ns_prior_draw_kernel, dim3(ns_blocks(n * prior->ndim)), dim3(256), 0, (hipStream_t)hip_stream, *prior, n, key, d_u,
                      d_theta);
-  return ns_launched("cf_ns_prior_draw");
+  return cf_launch_status("cf_ns_prior_draw");
 }
 
 extern "C" int cf_ns_transform(const cf_ns_prior* prior, const double* d_u, int64_t n, double* d_theta, void* hip_stream) {
@@ -180,7 +175,7 @@ extern "C" int cf_ns_transform(const cf_ns_prior* prior, const double* d_u, int6
   if (!d_u || !d_theta || n < 0) return cf_set_error(CF_ERR_INVALID, "cf_ns_transform: null argument or n < 0");
   if (n == 0) return CF_OK;
   hipLaunchKernelGGL(ns_transform_kernel, dim3(ns_blocks(n * prior->ndim)), dim3(256), 0, (hipStream_t)hip_stream, *prior, d_u, n, d_theta);
-  return ns_launched("cf_ns_transform");
+  return cf_launch_status("cf_ns_transform");
 }
 
 extern "C" int cf_ns_walk_start(const double* d_su, const double* d_stheta, const double* d_slogl, int64_t n_surv, int32_t ndim, int64_t m,
@@ -191,7 +186,7 @@ extern "C" int cf_ns_walk_start(const double* d_su, const double* d_stheta, cons
   if (m == 0) return CF_OK;
   hipLaunchKernelGGL(ns_walk_start_kernel, dim3(ns_blocks(m)), dim3(256), 0, (hipStream_t)hip_stream, d_su, d_stheta, d_slogl, n_surv,
                      (int)ndim, m, key, d_wu, d_wtheta, d_wlogl);
-  return ns_launched("cf_ns_walk_start");
+  return cf_launch_status("cf_ns_walk_start");
 }
 
 extern "C" int cf_ns_propose(const cf_ns_prior* prior, const double* d_su, int64_t n_surv, int64_t m, uint64_t key, double gamma,
@@ -204,7 +199,7 @@ extern "C" int cf_ns_propose(const cf_ns_prior* prior, const double* d_su, int64
   if (m == 0) return CF_OK;
   hipLaunchKernelGGL(ns_propose_kernel, dim3(ns_blocks(m)), dim3(256), 0, (hipStream_t)hip_stream, *prior, d_su, n_surv, m, key, gamma, sigma,
                      d_wu, d_wtheta, d_pu, d_ptheta, d_ok);
-  return ns_launched("cf_ns_propose");
+  return cf_launch_status("cf_ns_propose");
 }
 
 extern "C" int cf_ns_accept(int64_t m, int32_t ndim, const double* d_lstar, const double* d_pu, const double* d_ptheta, const int32_t* d_ok,
@@ -216,5 +211,5 @@ extern "C" int cf_ns_accept(int64_t m, int32_t ndim, const double* d_lstar, cons
   if (m == 0) return CF_OK;
   hipLaunchKernelGGL(ns_accept_kernel, dim3(ns_blocks(m)), dim3(256), 0, (hipStream_t)hip_stream, m, (int)ndim, d_lstar, d_pu, d_ptheta, d_ok,
                      d_plogl, d_wu, d_wtheta, d_wlogl, (unsigned long long*)d_counts);
-  return ns_launched("cf_ns_accept");
+  return cf_launch_status("cf_ns_accept");
 }

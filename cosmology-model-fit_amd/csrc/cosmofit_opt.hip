@@ -17,8 +17,7 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
+#include "cf_host.h"
 
 #define OPT_LANES 16  // lanes per problem in the direction kernel: lane i owns free coordinate i and row i of H^-1
 
@@ -344,10 +343,6 @@ static int opt_check_state(const cf_opt_state* s, const char* fn) {
 
 static unsigned opt_blocks(int64_t threads) { return (unsigned)((threads + 255) / 256); }
 
-static int opt_launched(const char* fn) {
-  return hipGetLastError() == hipSuccess ? CF_OK : cf_set_error(CF_ERR_HIP, std::string(fn) + ": launch failed");
-}
-
 extern "C" int cf_opt_starts(const cf_opt_params* params, int64_t n, const double* d_x0, uint64_t key, int32_t random, double* d_u,
                              double* d_theta, void* hip_stream) {
   int rc = opt_check_params(params, "cf_opt_starts");
@@ -356,7 +351,7 @@ extern "C" int cf_opt_starts(const cf_opt_params* params, int64_t n, const doubl
   if (n == 0) return CF_OK;
   hipLaunchKernelGGL(opt_starts_kernel, dim3(opt_blocks(n * params->ndim)), dim3(256), 0, (hipStream_t)hip_stream, *params, n, d_x0, key,
                      (int)(random != 0), d_u, d_theta);
-  return opt_launched("cf_opt_starts");
+  return cf_launch_status("cf_opt_starts");
 }
 
 extern "C" int cf_opt_stencil(const cf_opt_params* params, const cf_opt_state* state, const int32_t* d_active, int64_t n_active,
@@ -368,7 +363,7 @@ extern "C" int cf_opt_stencil(const cf_opt_params* params, const cf_opt_state* s
   if (n_active == 0) return CF_OK;
   hipLaunchKernelGGL(opt_stencil_kernel, dim3(opt_blocks(n_active * 2 * params->n_free * params->ndim)), dim3(256), 0,
                      (hipStream_t)hip_stream, *params, *state, d_active, n_active, d_rows);
-  return opt_launched("cf_opt_stencil");
+  return cf_launch_status("cf_opt_stencil");
 }
 
 extern "C" int cf_opt_direction(const cf_opt_params* params, const cf_opt_state* state, const int32_t* d_active, int64_t n_active,
@@ -381,7 +376,7 @@ extern "C" int cf_opt_direction(const cf_opt_params* params, const cf_opt_state*
   if (n_active == 0) return CF_OK;
   hipLaunchKernelGGL(opt_direction_kernel, dim3(opt_blocks(n_active * OPT_LANES)), dim3(256), 0, (hipStream_t)hip_stream, *params, *state,
                      d_active, n_active, d_fs, d_trials);
-  return opt_launched("cf_opt_direction");
+  return cf_launch_status("cf_opt_direction");
 }
 
 extern "C" int cf_opt_accept(const cf_opt_params* params, const cf_opt_state* state, const int32_t* d_active, int64_t n_active,
@@ -393,7 +388,7 @@ extern "C" int cf_opt_accept(const cf_opt_params* params, const cf_opt_state* st
   if (n_active == 0) return CF_OK;
   hipLaunchKernelGGL(opt_accept_kernel, dim3(opt_blocks(n_active)), dim3(256), 0, (hipStream_t)hip_stream, *params, *state, d_active,
                      n_active, d_ft);
-  return opt_launched("cf_opt_accept");
+  return cf_launch_status("cf_opt_accept");
 }
 
 extern "C" int cf_opt_compact(const int32_t* d_active, int64_t n_active, const int32_t* d_status, int32_t* d_next, int32_t* d_count,
@@ -401,5 +396,5 @@ extern "C" int cf_opt_compact(const int32_t* d_active, int64_t n_active, const i
   if (!d_active || !d_status || !d_next || !d_count || n_active < 0 || n_active > INT32_MAX)
     return cf_set_error(CF_ERR_INVALID, "cf_opt_compact: null argument or n_active out of range");
   hipLaunchKernelGGL(opt_compact_kernel, dim3(1), dim3(1024), 0, (hipStream_t)hip_stream, d_active, n_active, d_status, d_next, d_count);
-  return opt_launched("cf_opt_compact");
+  return cf_launch_status("cf_opt_compact");
 }

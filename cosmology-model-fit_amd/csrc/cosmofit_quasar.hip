@@ -32,10 +32,9 @@
 #include <vector>
 
 #include "../../include/cosmofit.h"
+#include "cf_host.h"
 #include "cf_wave_scan.h"
 #include "cosmofit_device.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
 #define QSR_TPB 256
 #define QSR_WAVES (QSR_TPB / 64)
@@ -402,9 +401,5 @@ int cf_qsr_launch(const cf_qsr_state* q, const double* theta, int64_t W, double*
   hipLaunchKernelGGL(qsr_walker_kernel, dim3((unsigned)W), dim3(QSR_TPB), lds, st, q->args, theta, W, delta, extra,
                      out_kind != CF_OUT_CHI2 ? 1 : 0, th_copy, q->parts, q->mu_sn, q->mu_q, q->bao);
   // a refused launch is this call's error: the kernels behind it would otherwise finish the evaluation on stale residuals
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess)
-    return cf_set_error(CF_ERR_HIP, std::string("cf_qsr_launch: qsr_walker_kernel (or an earlier HIP call of this thread): ") +
-                                        hipGetErrorString(err));
-  return 0;
+  return cf_launch_status("cf_qsr_launch: qsr_walker_kernel (or an earlier HIP call of this thread)");
 }

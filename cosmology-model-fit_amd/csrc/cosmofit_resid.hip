@@ -25,10 +25,9 @@
 #include <string>
 
 #include "../../include/cosmofit.h"
+#include "cf_host.h"
 #include "cosmofit_device.h"
 #include "cosmofit_resid.h"
-
-extern int cf_set_error(int code, const std::string& msg);  // cosmofit_api.hip
 
 #define RS_TPB 256
 #define RS_ROWS_PER_WG (RS_TPB / 64)
@@ -175,7 +174,5 @@ int cf_resid_launch(const cf_resid_src& src, int64_t rows, double* d_sample, con
     hipLaunchKernelGGL(resid_datum_kernel, dim3((unsigned)((src.n + RS_TPB - 1) / RS_TPB)), dim3(RS_TPB), 0, st, src, rows, d_w, thr,
                        *acc);
   }
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return cf_set_error(CF_ERR_HIP, std::string("cf_resid_device: ") + hipGetErrorString(err));
-  return CF_OK;
+  return cf_launch_status("cf_resid_device");
 }

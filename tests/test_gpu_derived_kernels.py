@@ -255,6 +255,23 @@ def test_host_twins_have_the_device_bits(pkg, lib, engines):
     assert _same_bits(eng.derived(th[3], ["Om", "rd"]), host[3, [names.index("Om"), names.index("rd")]])
 
 
+def test_cf_derived_beyond_one_piece_has_the_device_bits(pkg, lib, engines):
+    """cf_derived stages its rows through the device in pieces of 65536: 65537 rows cross one boundary, so the second piece's
+    row is read from behind the first's and its two columns land behind them."""
+    L, so = lib
+    case, S = "desi_cmb_thawing", 65537
+    eng, base = engines(case), DS.thetas(case)[:40]
+    th = np.ascontiguousarray(base[(7 * np.arange(S) + 3) % 40])
+    names = DS.applicable_scalars(pkg, case)[:2]
+    codes, args = _codes(pkg, names)
+    c = _consts(pkg, case)
+    out = np.full((S, 2), SENTINEL)
+    L.check(so.cf_derived(eng._h, th.ctypes.data, S, codes.ctypes.data_as(C.c_void_p), args.ctypes.data_as(C.c_void_p), 2,
+                          C.cast(C.pointer(c), C.c_void_p), out.ctypes.data))
+    assert np.isfinite(out).all() and (out != SENTINEL).all()
+    assert _same_bits(out, _derived(pkg, lib, eng, case, th, names))
+
+
 # ---- curves ------------------------------------------------------------------------------------------------------------------
 def _late_pchip_kwargs(pkg, n_grid):
     """likelihoods.DesiBao: late-time flat, thawing, h as the parameter, fixed r_d, D_H by PCHIP of the grid."""
@@ -336,6 +353,20 @@ def test_a_curve_row_keeps_its_bits_at_every_S_and_position(pkg, lib, curve_setu
             assert _same_bits(_curves(pkg, lib, eng, base[pick], z, q), ref[pick]), (name, q, S)
         wide = _curves(pkg, lib, eng, base[:5], np.concatenate([[0.7, 1.9], z, [0.2]]), q)  # ... and beside other redshifts
         assert _same_bits(wide[:, 2:4], ref[:5]), (name, q)
+
+
+def test_cf_curves_beyond_one_piece_has_the_device_bits(pkg, lib, curve_setup):
+    """cf_curves stages 65536 * 16 / nz rows per piece: at nz = 4096 that is 256, so 257 rows cross one boundary and the second
+    piece's curve lands behind the first 256."""
+    L, so = lib
+    eng, model, _ = curve_setup("late_pchip", 16)
+    S, nz = 257, 4096
+    th = np.ascontiguousarray(np.random.default_rng(6).uniform([0.55, 0.15, -1.0], [0.8, 0.45, -0.4], (S, 3)))
+    z = np.linspace(0.0, model.z_max, nz)
+    out = np.full((S, nz), SENTINEL)
+    L.check(so.cf_curves(eng._h, th.ctypes.data, S, L.CURVE_CODES["DM"], z.ctypes.data, nz, out.ctypes.data))
+    assert np.isfinite(out).all() and (out != SENTINEL).all()
+    assert _same_bits(out, _curves(pkg, lib, eng, th, z, "DM"))
 
 
 @pytest.mark.parametrize("n_grid", [16, 4000])

@@ -167,6 +167,37 @@ def test_host_pointers_give_the_bits_of_device_pointers(Q):
                 assert _bits(dev[k], np.ascontiguousarray(host[k])), (name, k)
 
 
+def test_host_pointers_beyond_one_piece_give_the_bits_of_device_pointers(pkg, Q):
+    """cf_field stages 2^22 / (its widest query set) rows per piece: with the 4096 scale factors a call accepts at most that is
+    1024, so 1025 rows cross one boundary and the second piece's row lands behind the first's in a per-point output, in scalars
+    and in status.  16 nodes keep it cheap."""
+    L, lib = pkg._lib, pkg.lib()
+    n_aq = L.CF_FIELD_MAX_NQ
+    S = (1 << 22) // n_aq + 1
+    theta = fs.theta_of("thawing", fs.physical("thawing", S, 17))
+    m = _model(Q, "thawing", 16)
+    a_q = np.exp(np.random.default_rng(18).uniform(np.log(1e-8), np.log(5.0), n_aq))
+    host = dict(phi_a=np.full((S, n_aq), SENTINEL), scalars=np.full((S, L.CF_FIELD_NSCALAR), SENTINEL), status=np.full(S, -1, dtype=np.int32))
+    q, o = L.cf_field_queries(), L.cf_field_out()
+    q.a_q, q.n_aq = a_q.ctypes.data, n_aq
+    for k, v in host.items():
+        setattr(o, k, v.ctypes.data)
+    L.check(lib.cf_field(C.byref(m._desc), theta.ctypes.data, S, C.byref(q), C.byref(o)))
+    x, daq = torch.from_numpy(theta).to(DEV), torch.from_numpy(a_q).to(DEV)
+    dev = dict(phi_a=torch.full((S, n_aq), SENTINEL, dtype=torch.float64, device=DEV),
+               scalars=torch.full((S, L.CF_FIELD_NSCALAR), SENTINEL, dtype=torch.float64, device=DEV),
+               status=torch.full((S,), -1, dtype=torch.int32, device=DEV))
+    q, o = L.cf_field_queries(), L.cf_field_out()
+    q.a_q, q.n_aq = daq.data_ptr(), n_aq
+    for k, v in dev.items():
+        setattr(o, k, v.data_ptr())
+    L.check(lib.cf_field_device(C.byref(m._desc), x.data_ptr(), S, C.byref(q), C.byref(o), torch.cuda.current_stream(DEV).cuda_stream))
+    assert host["status"].tolist() == [fs.planted("thawing", S).get(i, 0) for i in range(S)]
+    assert host["status"][S - 1] == 0 and (host["phi_a"][S - 1] != SENTINEL).all() and (host["scalars"][S - 1] != SENTINEL).all()
+    for k, v in dev.items():
+        assert _bits(host[k], v.cpu().numpy()), k
+
+
 def test_null_outputs_are_skipped_and_nothing_is_written_past_an_output(pkg, Q):
     L, lib = pkg._lib, pkg.lib()
     name, n_a, S, n = "thawing", 65, 2, 65

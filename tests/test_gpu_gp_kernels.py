@@ -222,6 +222,38 @@ def test_host_twins_give_the_device_entries_bits(lib, handles):
     L.check(so.cf_gp_mll(h, p(th), 0, None, None))  # zero rows: a no-op
 
 
+def test_cf_gp_mll_beyond_one_piece_gives_the_device_entrys_bits(lib, handles):
+    """cf_gp_mll stages its rows through the device in pieces of 16384: one row more crosses one boundary, so the second
+    piece's row is read from behind the first's and its out / parts land behind them.  n = 1 keeps it cheap."""
+    L, so = lib
+    n, piece = 1, 16384
+    h = handles(n)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    W = piece + 1
+    th = GS.thetas(n, W)
+    out, parts = np.full(W, SENTINEL), np.full((W, 2), SENTINEL)
+    L.check(so.cf_gp_mll(h, p(th), W, p(out), p(parts)))
+    out_d, parts_d = _mll(lib, h, th)
+    assert np.isfinite(out).all() and np.isfinite(parts).all() and (out != SENTINEL).all() and (parts != SENTINEL).all()
+    assert _same_bits(out, out_d) and _same_bits(parts, parts_d)
+    assert _failed(lib, h) == 0
+
+
+def test_cf_gp_predict_beyond_one_piece_gives_the_device_entrys_bits(lib, handles):
+    """As above for cf_gp_predict at the largest nz of these tests: the smallest S beyond one piece of 16384 * 256 / (5 nz) rows."""
+    L, so = lib
+    n, piece, nz = 1, 16384, GS.NZ_FULL
+    h = handles(n)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    S = max(1, piece * 256 // (nz * 5)) + 1
+    th, zs = GS.thetas(n, S), GS.z_star(n, nz)
+    pred = np.full((S, nz, 5), SENTINEL)
+    L.check(so.cf_gp_predict(h, p(th), S, p(zs), nz, GS.TEST_NOISE, p(pred)))
+    assert np.isfinite(pred).all() and (pred != SENTINEL).all()
+    assert _same_bits(pred, _predict(lib, h, th, zs, GS.TEST_NOISE))
+    assert _failed(lib, h) == 0
+
+
 def test_row_counts_beyond_one_grid_are_launched_in_pieces(lib, handles):
     """Rows are launched as grids of at most 2^22 workgroups: a batch one row longer than that takes a second grid.  n = 1
     keeps it cheap; the rows on either side of the seam and the last one carry the bits they have alone."""

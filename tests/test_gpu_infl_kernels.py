@@ -259,6 +259,31 @@ def test_a_row_has_the_same_bits_wherever_and_however_it_is_computed(pkg, I, cas
         I.set_library_chunk(eng, 0)
 
 
+def test_host_pointers_beyond_one_piece_have_the_bits_of_the_device_path(pkg, I):
+    """cf_infl stages its rows through the device in pieces of 4096: 4097 rows of the smallest SN engine cross one boundary, so
+    the second piece's rows land behind the first's in g and in the sample table, and the accumulator is continued across it."""
+    L, n, S, thr = pkg._lib, IS.N_SN[0], 4097, np.array(IS.THRESHOLDS)
+    lk, _ = RS.sn_likelihood(pkg, n)
+    eng = lk.engine
+    try:
+        theta = RS.sn_thetas(pkg, S)
+        dacc = I._Acc(n, thr.size, DEV)
+        dev = I._launch(eng, torch.from_numpy(theta).to(DEV), None, "sn", ("g",), True, thr, dacc, None)
+        out, arrs = IS.host_out(L, S, n, want=("g", "sample"))
+        hacc, harrs = RS.host_acc(L, n, thr.size)
+        L.check(pkg.lib().cf_infl(eng._h, eng.precision("sn")._p, theta.ctypes.data, S, None, L.RESID_BLOCKS["sn"], thr.ctypes.data,
+                                  thr.size, C.byref(out), C.byref(hacc), None))
+        assert np.isfinite(arrs["g"]).all() and np.isfinite(arrs["sample"]).all()
+        for key in ("g", "sample"):
+            assert np.array_equal(_bits(arrs[key]), _bits(dev[key].cpu().numpy())), key
+        for key in ("w_sum", "mean", "m2", "exceed"):
+            assert np.array_equal(_bits(harrs[key]), _bits(getattr(dacc, key).cpu().numpy())), key
+        assert harrs["n_used"][0] == S and np.array_equal(harrs["n_used"], dacc.n_used.cpu().numpy())
+        assert np.array_equal(harrs["n_skipped"], dacc.n_skipped.cpu().numpy())
+    finally:
+        eng.close()
+
+
 def test_only_what_was_asked_for_is_returned_and_no_rows_is_a_no_op(I, case):
     res = I.rows(case.engine, case.x[:40], case.block, want=("z",))
     assert set(res) == {"z", "sample"}

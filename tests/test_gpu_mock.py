@@ -228,6 +228,29 @@ def test_bits_do_not_depend_on_position_chunking_pointers_or_the_order_of_the_se
 
 
 # ---- 9: special rows ---------------------------------------------------------------------------------------------------------
+def test_host_pointers_beyond_one_piece_have_the_bits_of_the_device_path(pkg, M):
+    """cf_mock_eval stages its rows through the device in pieces of 65536: 65537 rows of the smallest SN engine cross one
+    boundary, so the second piece's row and mock index are read from behind the first's and its out / cross land behind them."""
+    L, n, S = pkg._lib, RS.N_SN[0], 65537
+    lk, syn = RS.sn_likelihood(pkg, n)
+    try:
+        d_sn = np.random.default_rng(32).standard_normal((N_MOCKS, n)) * np.sqrt(np.diag(syn["cov"]))
+        mset = M.MockSet.from_shifts(lk.engine, sn=d_sn)
+        theta = np.ascontiguousarray(RS.sn_thetas(pkg, S))
+        mock = np.arange(S, dtype=np.int32) % N_MOCKS
+        want, want_x = (t.cpu().numpy() for t in mset.log_prob(_dev(theta), _dev(mock), 0, cross=True))
+        g, hc = mset.g["sn"].cpu().numpy(), mset.c.cpu().numpy()
+        hs = L.cf_mock_set()
+        hs.struct_size, hs.n_mocks, hs.n_sn, hs.g_sn, hs.c = C.sizeof(L.cf_mock_set), N_MOCKS, n, g.ctypes.data, hc.ctypes.data
+        out, cross = np.full(S, np.nan), np.full((S, 3), np.nan)
+        L.check(pkg.lib().cf_mock_eval(lk.engine._h, C.byref(hs), theta.ctypes.data, S, mock.ctypes.data, 0, out.ctypes.data,
+                                       cross.ctypes.data))
+        assert np.isfinite(out).all() and np.isfinite(cross).all()
+        assert np.array_equal(_bits(out), _bits(want)) and np.array_equal(_bits(cross), _bits(want_x))
+    finally:
+        lk.engine.close()
+
+
 def test_special_rows(case, pkg):
     c = case
     S = 12

@@ -219,6 +219,32 @@ def test_datum_accumulators(pkg, F, case, weighted):
         F.set_library_chunk(eng, 0)
 
 
+def test_host_pointers_beyond_one_piece_have_the_bits_of_the_device_path(pkg, F):
+    """cf_resid stages its rows through the device in pieces of 65536: 65537 rows of the smallest SN engine cross one boundary,
+    so the second piece's row lands behind the first's in both tables, its weight is read from behind the first's, and the
+    accumulator is continued across it."""
+    L, n, S, thr = pkg._lib, RS.N_SN[0], 65537, np.array(RS.THRESHOLDS)
+    lk, _ = RS.sn_likelihood(pkg, n)
+    eng = lk.engine
+    try:
+        theta = RS.sn_thetas(pkg, S)
+        w = np.random.default_rng(4).uniform(0.0, 1.0, S)
+        w[::9] = 0.0
+        dacc = F.Accumulator(eng, "sn", thr, device=DEV)
+        d_sample, d_blocks = F._launch(eng, torch.from_numpy(theta).to(DEV), torch.from_numpy(w).to(DEV), "sn", dacc, True)
+        sample, blocks = np.full((S, len(R.COLUMNS)), np.nan), np.full((S, 10), np.nan)
+        hacc, arrs = RS.host_acc(L, n, thr.size)
+        L.check(pkg.lib().cf_resid(eng._h, theta.ctypes.data, S, w.ctypes.data, L.RESID_BLOCKS["sn"], thr.ctypes.data, thr.size,
+                                   sample.ctypes.data, blocks.ctypes.data, C.byref(hacc)))
+        assert np.isfinite(blocks).all() and np.isfinite(sample[:, 0]).all()
+        assert np.array_equal(_bits(sample), _bits(d_sample.cpu().numpy()))
+        assert np.array_equal(_bits(blocks), _bits(d_blocks.cpu().numpy()))
+        assert _same_state(arrs, _raw(dacc))
+        assert arrs["n_used"][0] + arrs["n_skipped"][0] == S and arrs["n_skipped"][0] == np.count_nonzero(w == 0.0)
+    finally:
+        eng.close()
+
+
 def test_report_is_one_pass_with_both_outputs(F, case):
     rep = F.report(case.engine, case.x, block=case.block, thresholds=(1.0, 2.0))
     assert np.array_equal(_bits(rep["stats"].cpu().numpy()), _bits(case.stats))
