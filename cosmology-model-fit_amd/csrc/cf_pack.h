@@ -38,7 +38,7 @@ static inline int cf_diag_ml_max(int NW, int v, int tiles_b) {
 }
 
 // Returns 0, or -1 when a pivot is not finite-positive.  (ksplit, tclasses) in {(1,4), (2,4), (4,4), (2,8)}.
-static int cf_pack_cholesky(const double* L, int64_t n, int64_t ld, cf_host_pack& out, int ksplit = 2, int tclasses = 4) {
+static inline int cf_pack_cholesky(const double* L, int64_t n, int64_t ld, cf_host_pack& out, int ksplit = 2, int tclasses = 4) {
   const int64_t n_pad = (n + 15) / 16 * 16;
   const int64_t T = n_pad / 16;
   const int n_blocks = (int)((T + CF_BLOCK_TILES - 1) / CF_BLOCK_TILES);
@@ -137,7 +137,7 @@ static int cf_pack_cholesky(const double* L, int64_t n, int64_t ld, cf_host_pack
 // structure (update through -L fragments per K-split group, diagonal through the inverse
 // fragments).  Used only by the CPU test-suite to validate the packing logic without a GPU;
 // cf_eval never calls it.
-static double cf_pack_replay_host(const cf_host_pack& pk, const double* b_in) {
+static inline double cf_pack_replay_host(const cf_host_pack& pk, const double* b_in) {
   const int64_t n_pad = pk.n_pad, T = n_pad / 16;
   const int KS = pk.ksplit, TC = pk.tclasses, NW = TC * KS, NTD = cf_diag_slots(NW);
   std::vector<double> y((size_t)n_pad, 0.0), rhs(CF_BLOCK_ROWS);
@@ -190,7 +190,7 @@ static double cf_pack_replay_host(const cf_host_pack& pk, const double* b_in) {
 // scatter.  A smooth right-hand side is the hard case for an explicit inverse: neighbouring (strongly correlated)
 // supernovae make rows of L^-1 large and alternating, and the products cancel.
 #define CF_PROBE_MODES 3
-static void cf_probe_rhs(int mode, int64_t n, std::vector<double>& b) {
+static inline void cf_probe_rhs(int mode, int64_t n, std::vector<double>& b) {
   b.resize((size_t)n);
   uint64_t s = 0x1234567ull;
   for (int64_t i = 0; i < n; ++i) {
@@ -206,7 +206,7 @@ static void cf_probe_rhs(int mode, int64_t n, std::vector<double>& b) {
 }
 
 // || L^-1 b ||^2 by plain row-by-row forward substitution (solve_triangular.py:12-14): what a probe compares with.
-static double cf_probe_reference(const double* L, int64_t n, int64_t ld, const std::vector<double>& b) {
+static inline double cf_probe_reference(const double* L, int64_t n, int64_t ld, const std::vector<double>& b) {
   std::vector<double> y((size_t)n);
   double ref = 0.0;
   for (int64_t i = 0; i < n; ++i) {
@@ -222,7 +222,7 @@ static double cf_probe_reference(const double* L, int64_t n, int64_t ld, const s
 // Accuracy probe of a packed factor: || L^-1 b ||^2 through the fragment streams (blocked, diagonal blocks through
 // their inverses) against row-by-row forward substitution, worst of the CF_PROBE_MODES right-hand sides.  An
 // ill-conditioned diagonal block shows up here (cond(L_bb) * eps) before any walker is evaluated.
-static double cf_pack_probe(const cf_host_pack& pk, const double* L, int64_t ld) {
+static inline double cf_pack_probe(const cf_host_pack& pk, const double* L, int64_t ld) {
   double worst = 0.0;
   std::vector<double> b;
   for (int mode = 0; mode < CF_PROBE_MODES; ++mode) {
@@ -255,7 +255,7 @@ struct cf_host_invpack {
 // four accumulation chains per dot product, and the stored double is the rounding of that extended result -- so an
 // entry of X carries one rounding, not the ~sqrt(n) eps of a double recurrence.  Columns are independent: a few host
 // threads share them (n^3 / 6 = 0.8 G multiply-adds at n = 1701).
-static void cf_invert_lower(const double* L, int64_t n, int64_t ld, int64_t n_pad, std::vector<double>& X) {
+static inline void cf_invert_lower(const double* L, int64_t n, int64_t ld, int64_t n_pad, std::vector<double>& X) {
   X.assign((size_t)n_pad * n_pad, 0.0);
   for (int64_t j = n; j < n_pad; ++j) X[(size_t)j * n_pad + j] = 1.0;
   unsigned nt = std::thread::hardware_concurrency();
@@ -299,7 +299,7 @@ static inline int64_t cf_inv_col(int64_t s2, int kq, int h) { return 8 * s2 + 2 
 // row blocks (four 16-row tiles = 64 rows) of the packed inverse of an n-row factor
 static inline int cf_inv_rowblocks(int64_t n) { return (int)(((n + 15) / 16 + 3) / 4); }
 
-static void cf_pack_inverse(const double* L, int64_t n, int64_t ld, cf_host_invpack& out) {
+static inline void cf_pack_inverse(const double* L, int64_t n, int64_t ld, cf_host_invpack& out) {
   const int64_t n_pad = (n + 15) / 16 * 16;
   const int RB = cf_inv_rowblocks(n);
   out.n = n;
@@ -333,7 +333,7 @@ static void cf_pack_inverse(const double* L, int64_t n, int64_t ld, cf_host_invp
     }
 }
 
-static double cf_invpack_replay_host(const cf_host_invpack& pk, const double* b_in) {
+static inline double cf_invpack_replay_host(const cf_host_invpack& pk, const double* b_in) {
   const int64_t n_ld = (int64_t)pk.n_rowblocks * 64;
   std::vector<double> b((size_t)n_ld + 64, 0.0);
   for (int64_t i = 0; i < pk.n; ++i) b[i] = b_in[i];
@@ -357,7 +357,7 @@ static double cf_invpack_replay_host(const cf_host_invpack& pk, const double* b_
 
 // Probe of the inverse pack: worst relative chi^2 discrepancy against row-by-row substitution over the
 // CF_PROBE_MODES right-hand sides (cf_probe_rhs).
-static double cf_invpack_probe(const cf_host_invpack& pk, const double* L, int64_t ld) {
+static inline double cf_invpack_probe(const cf_host_invpack& pk, const double* L, int64_t ld) {
   double worst = 0.0;
   // the solve kernels compute a stream's offset in closed form: a pack laid out differently must not reach them
   for (int rb = 0; rb < pk.n_rowblocks; ++rb)

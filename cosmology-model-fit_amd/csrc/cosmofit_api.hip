@@ -1,8 +1,9 @@
-// cosmofit_api.hip — host side of the C-ABI declared in include/cosmofit.h.
+// cosmofit_api.hip — the engine's host side of the C-ABI declared in include/cosmofit.h: cf_create, cf_eval* and the accessors.
 //
 // Owns device memory (data vectors, packed factor, per-call workspace), one HIP stream per
 // handle, and the launches of the kernels in cosmofit_kernels.hip.  There is NO CPU evaluation
-// path here: without a HIP device every entry point returns CF_ERR_NO_DEVICE.
+// path here: without a HIP device every entry point returns CF_ERR_NO_DEVICE.  The handle itself is cf_handle.h's; the host
+// code of each analysis feature (quasars, derived quantities, fit report, mocks, attribution) lies beside its kernels.
 #include <hip/hip_runtime.h>
 #include <sys/prctl.h>
 
@@ -22,13 +23,8 @@
 #include <vector>
 
 #include "../../include/cosmofit.h"
-#include "cf_host.h"
-#include "cf_pack.h"
+#include "cf_handle.h"
 #include "cf_stream_pack.h"
-#include "cosmofit_device.h"
-#include "cosmofit_group.h"
-#include "cosmofit_infl.h"
-#include "cosmofit_mock.h"
 #include "cosmofit_resid.h"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -239,62 +235,6 @@ static int fail(int code, const std::string& msg) {
 }
 int cf_set_error(int code, const std::string& msg) { return fail(code, msg); }  // cf_host.h: the other translation units' way in
 
-struct PackedFactor {
-  DevBuf frags, upd_off, diag_off;
-  cf_dev_pack dev{};
-  int64_t n = 0, n_pad = 0, bytes = 0;
-  int upload(const cf_host_pack& hp) {
-    n = hp.n;
-    n_pad = hp.n_pad;
-    bytes = (int64_t)(hp.frags.size() * sizeof(cf_d2));
-    if (frags.ensure(hp.frags.size() * sizeof(cf_d2) + 16)) return CF_ERR_HIP;
-    if (upd_off.ensure(hp.upd_off.size() * 8)) return CF_ERR_HIP;
-    if (diag_off.ensure(hp.diag_off.size() * 8)) return CF_ERR_HIP;
-    HIP_TRY(hipMemcpy(frags.p, hp.frags.data(), hp.frags.size() * sizeof(cf_d2), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(upd_off.p, hp.upd_off.data(), hp.upd_off.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(diag_off.p, hp.diag_off.data(), hp.diag_off.size() * 8, hipMemcpyHostToDevice));
-    dev.frags = frags.as<const cf_d2>();
-    dev.upd_off = upd_off.as<const int64_t>();
-    dev.diag_off = diag_off.as<const int64_t>();
-    dev.n_blocks = hp.n_blocks;
-    dev.ksplit = hp.ksplit;
-    dev.tclasses = hp.tclasses;
-    return 0;
-  }
-};
-
-struct InversePack {
-  DevBuf frags, off;
-  cf_dev_invpack dev{};
-  int64_t bytes = 0;
-  int upload(const cf_host_invpack& hp) {
-    bytes = (int64_t)(hp.frags.size() * sizeof(cf_d2));
-    if (frags.ensure(hp.frags.size() * sizeof(cf_d2))) return CF_ERR_HIP;
-    if (off.ensure(hp.off.size() * 8)) return CF_ERR_HIP;
-    HIP_TRY(hipMemcpy(frags.p, hp.frags.data(), hp.frags.size() * sizeof(cf_d2), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(off.p, hp.off.data(), hp.off.size() * 8, hipMemcpyHostToDevice));
-    dev.frags = frags.as<const cf_d2>();
-    dev.off = off.as<const int64_t>();
-    dev.n_rowblocks = hp.n_rowblocks;
-    return 0;
-  }
-};
-
-// Pinned host staging: pageable caller buffers make hipMemcpyAsync go through the runtime's own
-// bounce buffers; a handle-owned pinned block keeps the host round trip of a small batch short.
-struct PinnedBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-  int ensure(size_t need) {
-    if (need <= bytes) return 0;
-    if (p) { (void)hipHostFree(p); p = nullptr; bytes = 0; }
-    HIP_TRY(hipHostMalloc(&p, need, hipHostMallocDefault));
-    bytes = need;
-    return 0;
-  }
-};
-
 #ifndef CF_ZEROCOPY_DEFAULT
 #define CF_ZEROCOPY_DEFAULT 4096  // walkers; beyond, in-place access to the pinned block is no faster than two copy commands (profiles/r03_zerocopy_threshold.txt)
 #endif
@@ -307,88 +247,6 @@ struct PinnedBuf {
 #ifndef CF_NP2_FROM
 #define CF_NP2_FROM 512  // walkers: 32-walker panels in the throughput solve kernel beyond this batch size, 16-walker panels up to it
 #endif
-
-// The quasar Hubble-diagram likelihoods (cosmofit_quasar.hip): create-time tables and the per-walker kernel's launch.
-struct cf_qsr_state;
-int cf_qsr_prepare(const cf_desc* c, const cf_qsr_ext* e, int64_t n_ld, cf_qsr_state** out);
-void cf_qsr_free(cf_qsr_state* q);
-int64_t cf_qsr_n_qsr(const cf_qsr_state* q);
-int32_t cf_qsr_n_bao(const cf_qsr_state* q);
-void cf_qsr_set_outputs(cf_qsr_state* q, double* parts, double* mu_sn, double* mu_q, double* bao);
-int cf_qsr_launch(const cf_qsr_state* q, const double* theta, int64_t W, double* delta, double* extra, int out_kind, double* th_copy,
-                  hipStream_t st);
-
-// A host thread that evaluates one replica's slice of a multi-device cf_eval (one per replica beyond the first).
-struct cf_worker {
-  std::thread th;
-  std::mutex m;
-  std::condition_variable cv;
-  bool has_job = false, done = false, quit = false;
-  const double* theta = nullptr;
-  double* out = nullptr;
-  int64_t W = 0;
-  int out_kind = 0, rc = 0;
-  std::string err;
-};
-
-struct cf_handle {
-  int device = 0;
-  int solve_mode = 0;
-  PinnedBuf stage_in, stage_out;
-  InversePack ipack;
-  DevBuf partial, arrivals;  // inverse-GEMM solve: chi^2 shares per (row block, walker); arrival counters per panel
-  DevBuf partial4;           // small-batch solve: shares per (panel, row block, tile, walker), CF_SMALL_MAX_PANELS panels
-  DevBuf epi;                // device copy of `epi_host`: what the solve kernels' last arrivers read of the prior / output epilogue
-  cf_epilogue epi_host{};
-  hipStream_t stream = nullptr;  // host-buffer evaluations (cf_eval, cf_eval_parts)
-  // the ONE workspace is shared by every evaluation of this handle: an evaluation launched on a different stream
-  // than the previous one first waits (on the host) for that stream
-  hipStream_t last_stream = nullptr;
-  bool has_last = false;
-  // what cf_last_residuals reports: the batch size of the most recent evaluation and the layout its per-walker kernel was
-  // launched with (0 walker rows, 1 the small-batch solve's fragment order); -1 / 0 before the first evaluation
-  int64_t last_W = -1;
-  int last_layout = 0;
-  // timing ring: per evaluation 4 events (before the walker kernel, behind it, behind the small-block / growth kernels, behind the solve)
-  std::vector<hipEvent_t> ev;
-  int timing_slots = 0, timing_stride = 1;
-  int64_t timed_calls = 0, eval_calls = 0;
-  cf_dev_desc d{};
-  PackedFactor pack;
-  DevBuf z_cmb, z_hel, obs, sn_step, sn_rec, log10_tab;
-  DevBuf stream_rec, stream_row;  // the SN records in segment order and their rows (walker_stream_kernel: cf_stream_pack.h)
-  cf_stream_args sargs{};         // rec == null: the data do not fit the streaming form
-  DevBuf bao_z, bao_val, bao_inv_cov, bao_qty, gl_x, gl_w, fixed_mu, cc_z, cc_h, cc_inv_cov, nu_grid, ln_grid, nu_sw, ln_sw, exp2_tab, sn_lin, sn_dir;
-  DevBuf theta, out, delta, ypk, chi2_extra, nonfinite;
-  DevBuf fs8_z, fs8_val, fs8_inv_cov, fs8_fid, fs8_step_of, fs8_order, fs8_tab, fs8_pts;
-  DevBuf bao_nodes, bao_base;  // [max_walkers][n_bao][CF_BAO_NODES] table nodes for small_blocks_kernel; first node per datum
-  PinnedBuf done_flags;           // [CF_DONE_FLAGS] words the evaluation's last kernel sets as each panel's results reach the staging block
-  unsigned long long done_seq = 0;
-  int done_armed = 0;             // panels whose word the current synchronous call waits for (0: wait for the stream)
-  bool theta_on_host = false;     // set around a zero-copy evaluation: theta is the pinned staging block (reads cross the host link)
-  bool has_small_blocks = false;  // BAO and / or CMB block present
-  bool has_growth = false;        // growth-rate block present
-  cf_qsr_state* qsr = nullptr;    // a quasar likelihood (cf_create_quasar): its per-walker kernel replaces walker_kernel
-  int64_t max_walkers = 0;
-  double pack_probe_rel = 0.0;
-  int cu_count = 0;
-  char arch[64] = {0};
-  // replicas on further devices (owned by the primary handle) and their worker threads
-  std::vector<cf_handle*> peers;
-  std::vector<std::unique_ptr<cf_worker>> workers;
-  std::mutex mu;
-  // fit report (cf_resid_device): sqrt(C_ii) of the SN / BAO data, computed on the host at cf_create and uploaded at the first
-  // call; per-chunk outputs of the accessor path (mu_corr, bao_theory, the chi^2 shares); rows per chunk (0: CF_RESID_CHUNK)
-  std::vector<double> sigma_sn_host, sigma_bao_host;
-  DevBuf sigma_sn, sigma_bao, r_mc, r_bt, r_blk, r_snb, r_fsb;
-  bool sigma_uploaded = false;
-  int64_t resid_rows = 0, resid_chunk = 0;
-  int64_t mock_chunk = 0;  // rows per chunk of cf_mock_eval_device (0: CF_MOCK_CHUNK); it shares the fit report's chunk buffers
-  // attribution (cf_infl_device): per-chunk g = K r and the contrib / z rows the caller did not ask for but an accumulator reads,
-  // each [rows][n] and allocated when first needed; rows per chunk (0: CF_INFL_CHUNK).  The residual rows are the fit report's.
-  DevBuf i_g, i_contrib, i_z;
-  int64_t infl_chunk = 0;
-};
 
 // ------------------------------------------------------------------------------------------------
 extern "C" int cf_abi_version(void) { return CF_ABI_VERSION; }
@@ -422,12 +280,6 @@ static std::vector<double> swizzle_for_walker_threads(const std::vector<double>&
   return out;
 }
 
-static int upload_vec(DevBuf& b, const double* src, int64_t n) {
-  if (b.ensure((size_t)n * 8)) return CF_ERR_HIP;
-  HIP_TRY(hipMemcpy(b.p, src, (size_t)n * 8, hipMemcpyHostToDevice));
-  return 0;
-}
-
 // Reduction table of log10_tab (cosmofit_kernels.hip): 64 cells of [0.5, 1), {1 / centre, log10 centre}, each
 // correctly rounded from extended precision.
 static int upload_log10_table(DevBuf& b) {
@@ -437,19 +289,17 @@ static int upload_log10_table(DevBuf& b) {
     t[j].x = (double)(1.0L / c);
     t[j].y = (double)log10l(c);
   }
-  if (b.ensure(sizeof(t))) return CF_ERR_HIP;
-  HIP_TRY(hipMemcpy(b.p, t, sizeof(t), hipMemcpyHostToDevice));
-  return 0;
+  return upload(b, t, 64);
 }
 
 // Reduction table of exp_tab (cosmofit_kernels.hip): 2^(j/64), j < 64, correctly rounded from extended precision.
 static int upload_exp2_table(DevBuf& b) {
   double t[64];
   for (int j = 0; j < 64; ++j) t[j] = (double)exp2l((long double)j / 64.0L);
-  return upload_vec(b, t, 64);
+  return upload(b, t, 64);
 }
 
-static int ensure_workspace(cf_handle* h, int64_t W) {
+int ensure_workspace(cf_handle* h, int64_t W) {
   const int64_t w_pad = (W + 31) / 32 * 32;  // whole panels of the widest solve kernel (2 x 16 walkers)
   if (!h->done_flags.p) {  // completion words of synchronous zero-copy calls (every likelihood form)
     if (h->done_flags.ensure((size_t)CF_DONE_FLAGS * 8)) return CF_ERR_HIP;
@@ -486,7 +336,8 @@ static int ensure_workspace(cf_handle* h, int64_t W) {
   return 0;
 }
 
-static int validate_desc(const cf_desc* c) {
+// Argument errors are reported before any device work: everything a descriptor can be refused for without a device is refused here.
+int validate_desc(const cf_desc* c) {
   if (c->abi_version != CF_ABI_VERSION || c->struct_size != (int32_t)sizeof(cf_desc))
     return fail(CF_ERR_INVALID, "cf_create: descriptor ABI version / size mismatch (got version " +
                                     std::to_string(c->abi_version) + ", size " + std::to_string(c->struct_size) +
@@ -557,18 +408,19 @@ static int validate_desc(const cf_desc* c) {
   if (c->n_devices < -1 || c->n_devices > 64 || (c->n_devices > 0 && !c->devices))
     return fail(CF_ERR_INVALID, "cf_create: n_devices must be -1 (all), 0 (cf_desc.device) or 1..64 with a devices array");
   if (!(c->probe_limit >= 0.0)) return fail(CF_ERR_INVALID, "cf_create: probe_limit must be >= 0 (0 = default)");
+  for (int k = 0; c->bounds && k < c->ndim; ++k)
+    if (!(c->bounds[2 * k + 1] > c->bounds[2 * k])) return fail(CF_ERR_INVALID, "cf_create: bounds must satisfy lo < hi");
+  for (int g = 0; g < c->n_gauss; ++g)
+    if (c->gauss[g].idx < 0 || c->gauss[g].idx >= c->ndim) return fail(CF_ERR_INVALID, "cf_create: gauss idx");
+  for (int g = 0; g < c->n_chi2_gauss; ++g)
+    if (c->chi2_gauss[g].idx < 0 || c->chi2_gauss[g].idx >= c->ndim) return fail(CF_ERR_INVALID, "cf_create: chi2_gauss idx");
+  for (int64_t i = 0; i < c->n_sn; ++i) {
+    const double piv = c->sn_chol[i * c->sn_chol_ld + i];
+    if (!(piv > 0.0) || !std::isfinite(piv))
+      return fail(CF_ERR_NOT_POSDEF, "cf_create: the Cholesky factor has a non-positive or non-finite pivot");
+  }
   return 0;
 }
-
-// Host-side preparation shared by the replicas of a multi-device handle: the factor is packed (and, for the
-// inverse-GEMM solve, inverted in extended precision) once, then uploaded to every device.
-struct HostPrep {
-  bool packed = false;
-  int solve_mode = 0;
-  double probe_rel = 0.0;
-  cf_host_invpack ip;
-  cf_host_pack hp;
-};
 
 // Growth-rate data points for growth_kernel: the RK4 step that contains ln a_k, the data in step order (ascending a), and per
 // datum in that order a record of CF_FS8_REC doubles:
@@ -644,63 +496,8 @@ static void fs8_points(const cf_dev_desc& d, const double* zs, int n, std::vecto
   }
 }
 
-// An entry point's hold on its handle: h->mu locked and the handle's device current (cf_host.h: DeviceScope) until it returns.
-// The helpers that need both take a `const HandleScope&` and reach the handle through it.
-struct HandleScope {
-  cf_handle* const h;
-  std::lock_guard<std::mutex> lock;
-  DeviceScope on_device;
-  const hipError_t err;
-  explicit HandleScope(cf_handle* handle) : h(handle), lock(h->mu), on_device(h->device), err(on_device.err) {}
-};
-
-// sqrt of the diagonal of inverse(inv_cov) (Gauss-Jordan with partial pivoting in extended precision): the errors of the BAO data
-// as the fit report plots them.  A singular matrix gives NaN.
-static void resid_bao_sigma(const double* inv_cov, int n, std::vector<double>& out) {
-  std::vector<long double> a((size_t)n * 2 * n, 0.0L);
-  const int ld = 2 * n;
-  for (int i = 0; i < n; ++i) {
-    for (int j = 0; j < n; ++j) a[(size_t)i * ld + j] = inv_cov[(size_t)i * n + j];
-    a[(size_t)i * ld + n + i] = 1.0L;
-  }
-  bool ok = true;
-  for (int k = 0; k < n && ok; ++k) {
-    int p = k;
-    for (int i = k + 1; i < n; ++i)
-      if (fabsl(a[(size_t)i * ld + k]) > fabsl(a[(size_t)p * ld + k])) p = i;
-    if (!(fabsl(a[(size_t)p * ld + k]) > 0.0L) || !std::isfinite((double)a[(size_t)p * ld + k])) { ok = false; break; }
-    if (p != k)
-      for (int j = 0; j < ld; ++j) std::swap(a[(size_t)p * ld + j], a[(size_t)k * ld + j]);
-    const long double inv = 1.0L / a[(size_t)k * ld + k];
-    for (int j = 0; j < ld; ++j) a[(size_t)k * ld + j] *= inv;
-    for (int i = 0; i < n; ++i) {
-      if (i == k) continue;
-      const long double f = a[(size_t)i * ld + k];
-      if (f != 0.0L)
-        for (int j = 0; j < ld; ++j) a[(size_t)i * ld + j] -= f * a[(size_t)k * ld + j];
-    }
-  }
-  out.assign((size_t)n, std::nan(""));
-  if (ok)
-    for (int i = 0; i < n; ++i) out[(size_t)i] = (double)sqrtl(a[(size_t)i * ld + n + i]);
-}
-
-static int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** out) {
-  cf_handle* h = new cf_handle();
-  auto bail = [&](int code) { cf_destroy(h); return code; };
-  h->device = device;
-  DeviceScope on_device(h->device);
-  if (on_device.err != hipSuccess) return bail(fail(CF_ERR_HIP, "hipSetDevice failed"));
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, h->device) == hipSuccess) {
-    h->cu_count = prop.multiProcessorCount;
-    snprintf(h->arch, sizeof(h->arch), "%s", prop.gcnArchName);
-  }
-  if (strncmp(h->arch, "gfx950", 6) != 0)
-    return bail(fail(CF_ERR_UNSUPPORTED, std::string("cf_create: device is ") + h->arch + ", this library is built for gfx950 only"));
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(CF_ERR_HIP, "hipStreamCreate failed"));
-
-  cf_dev_desc& d = h->d;
+// Every field of cf_dev_desc that is copied or derived from a descriptor validate_desc has passed.  No HIP call.
+static void fill_desc(const cf_desc* c, cf_dev_desc& d) {
   d.ndim = c->ndim;
   d.n_grid = c->n_grid;
   d.ez_model = c->ez_model;
@@ -749,8 +546,6 @@ static int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** 
   for (int i = 0; i < 9; ++i) d.cmb_inv_cov[i] = c->cmb_inv_cov[i];
   d.n_cc = c->n_cc;
   d.cc_logdet = c->cc_logdet;
-  h->has_small_blocks = c->n_bao > 0 || c->cmb_mode != CF_CMB_NONE || c->n_cc > 0;
-  h->has_growth = c->n_fs8 > 0;
   d.n_fs8 = c->n_fs8;
   // 256 lanes per walker, 1 / 2 / 4 / 8 steps per lane: the request rounded up to 256, 512, 1024 (default), 2048.  Measured against
   // the scripts' own equation integrated to 1e-12 (tools/fs8_parity_probe.py, profiles/r03_fs8_parity.txt): 512 steps leave 4e-9 on
@@ -771,148 +566,125 @@ static int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** 
     for (int k = 0; k < c->ndim; ++k) {
       d.lo[k] = c->bounds[2 * k];
       d.hi[k] = c->bounds[2 * k + 1];
-      if (!(d.hi[k] > d.lo[k])) return bail(fail(CF_ERR_INVALID, "cf_create: bounds must satisfy lo < hi"));
       s += std::log(d.hi[k] - d.lo[k]);  // normalization = -sum(log(hi-lo)), sn/pantheon.py:77
     }
     d.log_norm = c->prior_norm_mode == 1 ? 0.0 : -s;  // ohd/cc_cmb.py:70-73 returns 0.0 inside the box
   }
   d.n_gauss = c->n_gauss;
   for (int g = 0; g < c->n_gauss; ++g) {
-    if (c->gauss[g].idx < 0 || c->gauss[g].idx >= c->ndim) return bail(fail(CF_ERR_INVALID, "cf_create: gauss idx"));
     d.gauss_idx[g] = c->gauss[g].idx;
     d.gauss_mean[g] = c->gauss[g].mean;
     d.gauss_sigma[g] = c->gauss[g].sigma;
   }
   d.n_chi2_gauss = c->n_chi2_gauss;
   for (int g = 0; g < c->n_chi2_gauss; ++g) {
-    if (c->chi2_gauss[g].idx < 0 || c->chi2_gauss[g].idx >= c->ndim)
-      return bail(fail(CF_ERR_INVALID, "cf_create: chi2_gauss idx"));
     d.chi2_gauss_idx[g] = c->chi2_gauss[g].idx;
     d.chi2_gauss_mean[g] = c->chi2_gauss[g].mean;
     d.chi2_gauss_sigma[g] = c->chi2_gauss[g].sigma;
   }
+}
 
-  if (c->n_sn > 0) {
-    std::vector<double> step((size_t)c->n_sn);
-    d.step_pm1 = 1;
-    for (int64_t i = 0; i < c->n_sn; ++i) {
-      step[i] = c->sn_step ? c->sn_step[i] : (c->sn_z_cmb[i] <= c->sn_z_turn ? 1.0 : -1.0);  // sn/pantheon.py:46
-      if (step[i] != 1.0 && step[i] != -1.0) d.step_pm1 = 0;
-    }
-    int rc;
-    if ((rc = upload_vec(h->z_cmb, c->sn_z_cmb, c->n_sn))) return bail(rc);
-    if ((rc = upload_vec(h->z_hel, c->sn_z_hel, c->n_sn))) return bail(rc);
-    if ((rc = upload_vec(h->obs, c->sn_obs, c->n_sn))) return bail(rc);
-    if ((rc = upload_vec(h->sn_step, step.data(), c->n_sn))) return bail(rc);
-    d.z_cmb = h->z_cmb.as<const double>();
-    d.z_hel = h->z_hel.as<const double>();
-    d.obs = h->obs.as<const double>();
-    d.sn_step = h->sn_step.as<const double>();
-    {
-      // one record per SN for the production loop; spare records so that its look-ahead (one stride of at most CF_SN_PARTS_MAX x
-      // 512 records) needs no bounds check
-      std::vector<cf_d4> rec((size_t)d.n_ld + CF_SN_REC_SLACK, cf_d4{1.0, 1.0, 1.0, 0.0});
-      for (int64_t i = 0; i < c->n_sn; ++i)
-        rec[i] = cf_d4{d.has_vstep ? 1.0 + c->sn_z_cmb[i] : c->sn_z_cmb[i], d.lin_in_rec ? c->sn_lin_coef[i] : step[i],
-                       1.0 + c->sn_z_hel[i], c->sn_obs[i]};
-      if (h->sn_rec.ensure(rec.size() * sizeof(cf_d4))) return bail(CF_ERR_HIP);
-      if (hipMemcpy(h->sn_rec.p, rec.data(), rec.size() * sizeof(cf_d4), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(CF_ERR_HIP, "hipMemcpy(sn_rec) failed"));
-      d.sn_rec = h->sn_rec.as<const cf_d4>();
-      // the same records in the order the streaming form evaluates them (by grid segment of z_cmb), with their rows
-      cf_stream_plan plan;
-      if (d.chunk_shift == 3 &&
-          cf_stream_assign(c->sn_z_cmb, (d.has_vstep && !d.lin_in_rec) ? step.data() : nullptr, c->n_sn, d.n_grid, d.inv_step, d.z_max, plan)) {
-        std::vector<cf_d4> srec((size_t)c->n_sn + CF_STREAM_REC_SLACK, cf_d4{1.0, 1.0, 1.0, 0.0});
-        std::vector<int32_t> srow((size_t)c->n_sn + CF_STREAM_REC_SLACK, 0);
-        for (int64_t j = 0; j < c->n_sn; ++j) {
-          srow[(size_t)j] = plan.row[(size_t)j];
-          srec[(size_t)j] = rec[(size_t)plan.row[(size_t)j]];
-        }
-        int rcs;
-        if ((rcs = upload_vec(h->stream_rec, reinterpret_cast<const double*>(srec.data()), (int64_t)srec.size() * 4))) return bail(rcs);
-        if (h->stream_row.ensure(srow.size() * sizeof(int32_t))) return bail(CF_ERR_HIP);
-        if (hipMemcpy(h->stream_row.p, srow.data(), srow.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
-          return bail(fail(CF_ERR_HIP, "hipMemcpy(stream_row) failed"));
-        h->sargs.rec = h->stream_rec.as<const cf_d4>();
-        h->sargs.row = h->stream_row.as<const int32_t>();
-        for (int s = 0; s <= CF_STREAM_MAX_SEGS; ++s) h->sargs.seg_off[s] = plan.seg_off[s];
-        h->sargs.n_seg = plan.n_seg;
-        // the wave priority per segment (cf_stream_levels); CF_TUNE walker_level=0: every wave at priority 0 throughout
-        static const bool level_on = cf_tune("walker_level", 1) != 0;
-        int32_t level[CF_STREAM_MAX_SEGS] = {};
-        if (level_on) cf_stream_levels(plan.seg_off, plan.n_seg, level);
-        h->sargs.levels = cf_stream_levels_packed(level);
-        h->sargs.max_step = plan.max_step;
-        h->sargs.zp1_max = plan.zp1_max;
-      }
-      int rc2;
-      if ((rc2 = upload_log10_table(h->log10_tab))) return bail(rc2);
-      d.log10_tab = h->log10_tab.p;
-    }
-    for (int64_t i = 0; i < c->n_sn; ++i) {
-      const double piv = c->sn_chol[i * c->sn_chol_ld + i];
-      if (!(piv > 0.0) || !std::isfinite(piv))
-        return bail(fail(CF_ERR_NOT_POSDEF, "cf_create: the Cholesky factor has a non-positive or non-finite pivot"));
-    }
-    // sqrt(C_ii) = |row i of L| for the fit report (cf_resid_device): the factor is not kept on the host
-    h->sigma_sn_host.resize((size_t)c->n_sn);
-    for (int64_t i = 0; i < c->n_sn; ++i) {
-      long double acc = 0.0L;
-      const double* row = c->sn_chol + i * c->sn_chol_ld;
-      for (int64_t j = 0; j <= i; ++j) acc += (long double)row[j] * row[j];
-      h->sigma_sn_host[(size_t)i] = (double)sqrtl(acc);
-    }
-    if (!prep.packed) {
-      const double limit = c->probe_limit > 0.0 ? c->probe_limit : CF_PROBE_LIMIT;
-      prep.solve_mode = c->solve_mode;
-      if (c->solve_mode != CF_SOLVE_BLOCKED_TRSM) {
-        cf_pack_inverse(c->sn_chol, c->n_sn, c->sn_chol_ld, prep.ip);
-        const double inv_probe = cf_invpack_probe(prep.ip, c->sn_chol, c->sn_chol_ld);
-        if (inv_probe <= limit) {
-          prep.solve_mode = CF_SOLVE_INVERSE_GEMM;
-          prep.probe_rel = inv_probe;
-        } else if (c->solve_mode == CF_SOLVE_INVERSE_GEMM) {
-          return bail(fail(CF_ERR_ILL_CONDITIONED, "cf_create: the explicit inverse of the factor disagrees with row-by-row forward "
-                                                       "substitution by " + fmt_g(inv_probe) + " relative (limit " +
-                                                       fmt_g(limit) + "); use CF_SOLVE_BLOCKED_TRSM or CF_SOLVE_AUTO for "
-                                                       "this covariance"));
-        } else {
-          prep.solve_mode = CF_SOLVE_BLOCKED_TRSM;  // CF_SOLVE_AUTO falls back to forward substitution by blocks
-          prep.ip = cf_host_invpack();
-        }
-      }
-      if (prep.solve_mode == CF_SOLVE_BLOCKED_TRSM) {
-        if (pack_default(c->sn_chol, c->n_sn, c->sn_chol_ld, prep.hp, &prep.probe_rel) != 0)
-          return bail(fail(CF_ERR_NOT_POSDEF, "cf_create: the Cholesky factor has a non-positive or non-finite pivot"));
-        // the blocked solve inverts only 256-row diagonal blocks: its limit is the library's, not the caller's
-        if (!(prep.probe_rel <= CF_PROBE_LIMIT))
-          return bail(fail(CF_ERR_ILL_CONDITIONED, "cf_create: the blocked solve disagrees with row-by-row forward substitution by " +
-                                                       fmt_g(prep.probe_rel) + " relative on a probe vector (limit 1e-11): "
-                                                       "the factor's diagonal blocks are too ill-conditioned for 256-row block inverses"));
-      }
-      prep.packed = true;
-    }
-    h->solve_mode = prep.solve_mode;
-    h->pack_probe_rel = prep.probe_rel;
-    if (h->solve_mode == CF_SOLVE_INVERSE_GEMM) {
-      if ((rc = h->ipack.upload(prep.ip))) return bail(rc);
+// The SN records in the order the streaming form evaluates them (by grid segment of z_cmb), with their rows; nothing for data
+// that form does not take.
+static int upload_stream_plan(const cf_desc* c, const std::vector<double>& step, const std::vector<cf_d4>& rec, cf_handle* h) {
+  const cf_dev_desc& d = h->d;
+  cf_stream_plan plan;
+  if (d.chunk_shift != 3 ||
+      !cf_stream_assign(c->sn_z_cmb, (d.has_vstep && !d.lin_in_rec) ? step.data() : nullptr, c->n_sn, d.n_grid, d.inv_step, d.z_max, plan))
+    return 0;
+  std::vector<cf_d4> srec((size_t)c->n_sn + CF_STREAM_REC_SLACK, cf_d4{1.0, 1.0, 1.0, 0.0});
+  std::vector<int32_t> srow((size_t)c->n_sn + CF_STREAM_REC_SLACK, 0);
+  for (int64_t j = 0; j < c->n_sn; ++j) {
+    srow[(size_t)j] = plan.row[(size_t)j];
+    srec[(size_t)j] = rec[(size_t)plan.row[(size_t)j]];
+  }
+  int rc;
+  if ((rc = upload(h->stream_rec, srec.data(), (int64_t)srec.size(), h->sargs.rec)) ||
+      (rc = upload(h->stream_row, srow.data(), (int64_t)srow.size(), h->sargs.row)))
+    return rc;
+  for (int s = 0; s <= CF_STREAM_MAX_SEGS; ++s) h->sargs.seg_off[s] = plan.seg_off[s];
+  h->sargs.n_seg = plan.n_seg;
+  // the wave priority per segment (cf_stream_levels); CF_TUNE walker_level=0: every wave at priority 0 throughout
+  static const bool level_on = cf_tune("walker_level", 1) != 0;
+  int32_t level[CF_STREAM_MAX_SEGS] = {};
+  if (level_on) cf_stream_levels(plan.seg_off, plan.n_seg, level);
+  h->sargs.levels = cf_stream_levels_packed(level);
+  h->sargs.max_step = plan.max_step;
+  h->sargs.zp1_max = plan.zp1_max;
+  return 0;
+}
+
+// The factor of one cf_create, packed (and, for the inverse-GEMM solve, inverted in extended precision) and probed on the host.
+static int pack_factor(const cf_desc* c, HostPrep& prep) {
+  const double limit = c->probe_limit > 0.0 ? c->probe_limit : CF_PROBE_LIMIT;
+  prep.solve_mode = c->solve_mode;
+  if (c->solve_mode != CF_SOLVE_BLOCKED_TRSM) {
+    cf_pack_inverse(c->sn_chol, c->n_sn, c->sn_chol_ld, prep.ip);
+    const double inv_probe = cf_invpack_probe(prep.ip, c->sn_chol, c->sn_chol_ld);
+    if (inv_probe <= limit) {
+      prep.solve_mode = CF_SOLVE_INVERSE_GEMM;
+      prep.probe_rel = inv_probe;
+    } else if (c->solve_mode == CF_SOLVE_INVERSE_GEMM) {
+      return fail(CF_ERR_ILL_CONDITIONED, "cf_create: the explicit inverse of the factor disagrees with row-by-row forward "
+                                          "substitution by " + fmt_g(inv_probe) + " relative (limit " + fmt_g(limit) +
+                                          "); use CF_SOLVE_BLOCKED_TRSM or CF_SOLVE_AUTO for this covariance");
     } else {
-      if ((rc = h->pack.upload(prep.hp))) return bail(rc);
+      prep.solve_mode = CF_SOLVE_BLOCKED_TRSM;  // CF_SOLVE_AUTO falls back to forward substitution by blocks
+      prep.ip = cf_host_invpack();
     }
   }
+  if (prep.solve_mode == CF_SOLVE_BLOCKED_TRSM) {
+    if (pack_default(c->sn_chol, c->n_sn, c->sn_chol_ld, prep.hp, &prep.probe_rel) != 0)
+      return fail(CF_ERR_NOT_POSDEF, "cf_create: the Cholesky factor has a non-positive or non-finite pivot");
+    // the blocked solve inverts only 256-row diagonal blocks: its limit is the library's, not the caller's
+    if (!(prep.probe_rel <= CF_PROBE_LIMIT))
+      return fail(CF_ERR_ILL_CONDITIONED, "cf_create: the blocked solve disagrees with row-by-row forward substitution by " +
+                                          fmt_g(prep.probe_rel) + " relative on a probe vector (limit 1e-11): "
+                                          "the factor's diagonal blocks are too ill-conditioned for 256-row block inverses");
+  }
+  prep.packed = true;
+  return 0;
+}
+
+// SN block: the data vectors, one record per SN, the streaming plan and the packed factor (packed once for all replicas).
+static int upload_sn(const cf_desc* c, HostPrep& prep, cf_handle* h) {
+  cf_dev_desc& d = h->d;
+  std::vector<double> step((size_t)c->n_sn);
+  d.step_pm1 = 1;
+  for (int64_t i = 0; i < c->n_sn; ++i) {
+    step[i] = c->sn_step ? c->sn_step[i] : (c->sn_z_cmb[i] <= c->sn_z_turn ? 1.0 : -1.0);  // sn/pantheon.py:46
+    if (step[i] != 1.0 && step[i] != -1.0) d.step_pm1 = 0;
+  }
+  int rc;
+  if ((rc = upload(h->z_cmb, c->sn_z_cmb, c->n_sn, d.z_cmb)) || (rc = upload(h->z_hel, c->sn_z_hel, c->n_sn, d.z_hel)) ||
+      (rc = upload(h->obs, c->sn_obs, c->n_sn, d.obs)) || (rc = upload(h->sn_step, step.data(), c->n_sn, d.sn_step)))
+    return rc;
+  // one record per SN for the production loop; spare records so that its look-ahead (one stride of at most CF_SN_PARTS_MAX x
+  // 512 records) needs no bounds check
+  std::vector<cf_d4> rec((size_t)d.n_ld + CF_SN_REC_SLACK, cf_d4{1.0, 1.0, 1.0, 0.0});
+  for (int64_t i = 0; i < c->n_sn; ++i)
+    rec[i] = cf_d4{d.has_vstep ? 1.0 + c->sn_z_cmb[i] : c->sn_z_cmb[i], d.lin_in_rec ? c->sn_lin_coef[i] : step[i],
+                   1.0 + c->sn_z_hel[i], c->sn_obs[i]};
+  if ((rc = upload(h->sn_rec, rec.data(), (int64_t)rec.size(), d.sn_rec)) || (rc = upload_stream_plan(c, step, rec, h)) ||
+      (rc = upload_log10_table(h->log10_tab)))
+    return rc;
+  d.log10_tab = h->log10_tab.p;
+  resid_sn_sigma(c->sn_chol, c->n_sn, c->sn_chol_ld, h->sigma_sn_host);
+  if (!prep.packed && (rc = pack_factor(c, prep))) return rc;
+  h->solve_mode = prep.solve_mode;
+  h->pack_probe_rel = prep.probe_rel;
+  return h->solve_mode == CF_SOLVE_INVERSE_GEMM ? h->ipack.upload(prep.ip) : h->pack.upload(prep.hp);
+}
+
+// BAO block, and for every BAO / growth-rate datum the first of the table nodes copied out for it.
+static int upload_bao_aux(const cf_desc* c, cf_handle* h) {
+  cf_dev_desc& d = h->d;
+  int rc;
   if (c->n_bao > 0) {
-    int rc;
-    if ((rc = upload_vec(h->bao_z, c->bao_z, c->n_bao))) return bail(rc);
-    if ((rc = upload_vec(h->bao_val, c->bao_val, c->n_bao))) return bail(rc);
-    if ((rc = upload_vec(h->bao_inv_cov, c->bao_inv_cov, (int64_t)c->n_bao * c->n_bao))) return bail(rc);
-    if (h->bao_qty.ensure((size_t)c->n_bao * 4)) return bail(CF_ERR_HIP);
-    if (hipMemcpy(h->bao_qty.p, c->bao_qty, (size_t)c->n_bao * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(CF_ERR_HIP, "hipMemcpy(bao_qty) failed"));
-    d.bao_z = h->bao_z.as<const double>();
-    d.bao_val = h->bao_val.as<const double>();
-    d.bao_inv_cov = h->bao_inv_cov.as<const double>();
-    d.bao_qty = h->bao_qty.as<const int32_t>();
+    if ((rc = upload(h->bao_z, c->bao_z, c->n_bao, d.bao_z)) || (rc = upload(h->bao_val, c->bao_val, c->n_bao, d.bao_val)) ||
+        (rc = upload(h->bao_inv_cov, c->bao_inv_cov, (int64_t)c->n_bao * c->n_bao, d.bao_inv_cov)) ||
+        (rc = upload(h->bao_qty, c->bao_qty, c->n_bao, d.bao_qty)))
+      return rc;
     resid_bao_sigma(c->bao_inv_cov, c->n_bao, h->sigma_bao_host);
   }
   if (d.n_aux > 0) {
@@ -921,63 +693,65 @@ static int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** 
     // and the two 3-point PCHIP stencils all stay inside the copy
     std::vector<int32_t> base((size_t)d.n_aux);
     for (int k = 0; k < d.n_aux; ++k) base[k] = aux_node_base(d, k < c->n_bao ? c->bao_z[k] : c->fs8_z[k - c->n_bao]);
-    if (h->bao_base.ensure(base.size() * 4)) return bail(CF_ERR_HIP);
-    if (hipMemcpy(h->bao_base.p, base.data(), base.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(CF_ERR_HIP, "hipMemcpy(bao_base) failed"));
-    d.bao_base = h->bao_base.as<const int32_t>();
+    if ((rc = upload(h->bao_base, base.data(), (int64_t)base.size(), d.bao_base))) return rc;
   }
-  if (c->n_fs8 > 0) {
-    int rc;
-    const int n = c->n_fs8;
-    if ((rc = upload_vec(h->fs8_z, c->fs8_z, n))) return bail(rc);
-    if ((rc = upload_vec(h->fs8_val, c->fs8_val, n))) return bail(rc);
-    if ((rc = upload_vec(h->fs8_inv_cov, c->fs8_inv_cov, (int64_t)n * n))) return bail(rc);
-    if ((rc = upload_vec(h->fs8_fid, c->fs8_fid, n))) return bail(rc);
-    d.fs8_z = h->fs8_z.as<const double>();
-    d.fs8_val = h->fs8_val.as<const double>();
-    d.fs8_inv_cov = h->fs8_inv_cov.as<const double>();
-    d.fs8_fid = h->fs8_fid.as<const double>();
-    // RK4 step that contains ln a_k, the data in step order (ascending a), their Hermite weights
-    const double x0 = std::log(c->fs8_a_init), hstep = -x0 / d.fs8_steps;
-    std::vector<int32_t> step_of, order;
-    std::vector<double> pts;
-    fs8_points(d, c->fs8_z, n, step_of, order, pts);
-    if (h->fs8_step_of.ensure((size_t)n * 4) || h->fs8_order.ensure((size_t)n * 4)) return bail(CF_ERR_HIP);
-    if (hipMemcpy(h->fs8_step_of.p, step_of.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(h->fs8_order.p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(CF_ERR_HIP, "hipMemcpy(fs8 order) failed"));
-    d.fs8_step_of = h->fs8_step_of.as<const int32_t>();
-    d.fs8_order = h->fs8_order.as<const int32_t>();
-    // what the ODE's coefficients need that does not depend on theta, at the 2 S + 1 boundaries and midpoints of the steps:
-    // a = exp(x), 1 + z, the massive-neutrino density ratio and nu 3 (1 + w_nu) / (1 + z)   cmb/data_planck_act_compression.py:53-83
-    const int npts = 2 * d.fs8_steps + 1;
-    std::vector<double> tab((size_t)(2 * (d.fs8_steps / 256)) * 257 * 4, 0.0);
-    for (int m = 0; m < npts; ++m) {
-      const double a = m == npts - 1 ? 1.0 : std::exp(x0 + m * (0.5 * hstep)), zp1 = 1.0 / a;
-      double nu = 0.0, dnu = 0.0;
-      if (c->ez_model == CF_EZ_PHYSICAL) {
-        const double r = c->nu_m0 / zp1, mz_sq = r * r;
-        double ws = 0.0, num = 0.0, den = 0.0;
-        for (int i = 0; i < 5; ++i) {
-          const double f = std::sqrt(c->nu_qs_sq[i] + mz_sq);
-          ws += f * c->nu_ws[i];
-          num += c->nu_ws[i] / f;
-          den += c->nu_ws[i] * f;
-        }
-        nu = zp1 * zp1 * zp1 * zp1 * ws / c->nu_rho0;
-        const double w_nu = (1.0 / 3) - (1.0 / 3) * mz_sq * num / den;
-        dnu = nu * 3 * (1.0 + w_nu) / zp1;
+  return 0;
+}
+
+// What the growth ODE's coefficients need that does not depend on theta, at the 2 S + 1 boundaries and midpoints of the steps:
+// a = exp(x), 1 + z, the massive-neutrino density ratio and nu 3 (1 + w_nu) / (1 + z)   cmb/data_planck_act_compression.py:53-83
+static std::vector<double> fs8_coef_table(const cf_desc* c, const cf_dev_desc& d) {
+  const double x0 = std::log(c->fs8_a_init), hstep = -x0 / d.fs8_steps;
+  const int npts = 2 * d.fs8_steps + 1;
+  std::vector<double> tab((size_t)(2 * (d.fs8_steps / 256)) * 257 * 4, 0.0);
+  for (int m = 0; m < npts; ++m) {
+    const double a = m == npts - 1 ? 1.0 : std::exp(x0 + m * (0.5 * hstep)), zp1 = 1.0 / a;
+    double nu = 0.0, dnu = 0.0;
+    if (c->ez_model == CF_EZ_PHYSICAL) {
+      const double r = c->nu_m0 / zp1, mz_sq = r * r;
+      double ws = 0.0, num = 0.0, den = 0.0;
+      for (int i = 0; i < 5; ++i) {
+        const double f = std::sqrt(c->nu_qs_sq[i] + mz_sq);
+        ws += f * c->nu_ws[i];
+        num += c->nu_ws[i] / f;
+        den += c->nu_ws[i] * f;
       }
-      // stored in the order the 256 lanes of growth_kernel fetch it: point m at [(m % 2C) * 257 + m / 2C], C = steps / 256
-      const int c2 = 2 * (d.fs8_steps / 256);
-      const size_t at = (size_t)(m % c2) * 257 + (size_t)(m / c2);
-      tab[4 * at] = a; tab[4 * at + 1] = zp1; tab[4 * at + 2] = nu; tab[4 * at + 3] = dnu;
+      nu = zp1 * zp1 * zp1 * zp1 * ws / c->nu_rho0;
+      const double w_nu = (1.0 / 3) - (1.0 / 3) * mz_sq * num / den;
+      dnu = nu * 3 * (1.0 + w_nu) / zp1;
     }
-    if ((rc = upload_vec(h->fs8_tab, tab.data(), (int64_t)tab.size()))) return bail(rc);
-    d.fs8_tab = h->fs8_tab.as<const double>();
-    if ((rc = upload_vec(h->fs8_pts, pts.data(), (int64_t)pts.size()))) return bail(rc);
-    d.fs8_pts = h->fs8_pts.as<const double>();
+    // stored in the order the 256 lanes of growth_kernel fetch it: point m at [(m % 2C) * 257 + m / 2C], C = steps / 256
+    const int c2 = 2 * (d.fs8_steps / 256);
+    const size_t at = (size_t)(m % c2) * 257 + (size_t)(m / c2);
+    tab[4 * at] = a; tab[4 * at + 1] = zp1; tab[4 * at + 2] = nu; tab[4 * at + 3] = dnu;
   }
+  return tab;
+}
+
+// Growth-rate block: the data, their RK4 steps and Hermite weights in step order (fs8_points), the ODE's coefficient table.
+static int upload_growth(const cf_desc* c, cf_handle* h) {
+  cf_dev_desc& d = h->d;
+  const int n = c->n_fs8;
+  int rc;
+  if ((rc = upload(h->fs8_z, c->fs8_z, n, d.fs8_z)) || (rc = upload(h->fs8_val, c->fs8_val, n, d.fs8_val)) ||
+      (rc = upload(h->fs8_inv_cov, c->fs8_inv_cov, (int64_t)n * n, d.fs8_inv_cov)) || (rc = upload(h->fs8_fid, c->fs8_fid, n, d.fs8_fid)))
+    return rc;
+  std::vector<int32_t> step_of, order;
+  std::vector<double> pts;
+  fs8_points(d, c->fs8_z, n, step_of, order, pts);
+  const std::vector<double> tab = fs8_coef_table(c, d);
+  if ((rc = upload(h->fs8_step_of, step_of.data(), n, d.fs8_step_of)) || (rc = upload(h->fs8_order, order.data(), n, d.fs8_order)) ||
+      (rc = upload(h->fs8_tab, tab.data(), (int64_t)tab.size(), d.fs8_tab)) || (rc = upload(h->fs8_pts, pts.data(), (int64_t)pts.size(), d.fs8_pts)))
+    return rc;
+  return 0;
+}
+
+// The theta-independent tables of the distance grid: the massive-neutrino density and ln(1 + z) at the nodes, each also in the
+// fetch order of walker_kernel's register path (chunk_shift == 3), and the two reduction tables of exp_tab / log10_tab.
+static int upload_grid_tables(const cf_desc* c, cf_handle* h) {
+  cf_dev_desc& d = h->d;
+  const bool power_law_de = c->fde == CF_FDE_WCDM || c->fde == CF_FDE_CPL;
+  int rc;
   if (c->ez_model == CF_EZ_PHYSICAL) {
     // massive-neutrino density at the grid nodes, cmb/data_planck_act_compression.py:53-66 -- independent of theta
     std::vector<double> nu((size_t)c->n_grid);
@@ -990,90 +764,98 @@ static int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** 
       const double zp1_2 = zp1 * zp1;
       nu[g] = zp1_2 * zp1_2 * ws / c->nu_rho0;
     }
-    int rc;
-    if ((rc = upload_vec(h->nu_grid, nu.data(), c->n_grid))) return bail(rc);
-    d.nu_grid = h->nu_grid.as<const double>();
+    if ((rc = upload(h->nu_grid, nu.data(), c->n_grid, d.nu_grid))) return rc;
     if (d.chunk_shift == 3) {
       const std::vector<double> sw = swizzle_for_walker_threads(nu);
-      if ((rc = upload_vec(h->nu_sw, sw.data(), (int64_t)sw.size()))) return bail(rc);
-      d.nu_sw = h->nu_sw.as<const double>();
+      if ((rc = upload(h->nu_sw, sw.data(), (int64_t)sw.size(), d.nu_sw))) return rc;
     }
   }
-  if (c->fde == CF_FDE_WCDM || c->fde == CF_FDE_CPL) {
+  if (power_law_de) {
     // ln(1 + z) at the grid nodes, correctly rounded from extended precision: the power-law dark-energy forms become one exp
     std::vector<double> ln((size_t)c->n_grid);
     for (int g = 0; g < c->n_grid; ++g) {
       const double z = g == c->n_grid - 1 ? c->z_max : (double)g * d.step;
       ln[g] = (double)log1pl((long double)z);
     }
-    int rc;
-    if ((rc = upload_vec(h->ln_grid, ln.data(), c->n_grid))) return bail(rc);
-    d.ln_grid = h->ln_grid.as<const double>();
+    if ((rc = upload(h->ln_grid, ln.data(), c->n_grid, d.ln_grid))) return rc;
     if (d.chunk_shift == 3) {
       const std::vector<double> sw = swizzle_for_walker_threads(ln);
-      if ((rc = upload_vec(h->ln_sw, sw.data(), (int64_t)sw.size()))) return bail(rc);
-      d.ln_sw = h->ln_sw.as<const double>();
-      // 2^(j/64), correctly rounded from extended precision: reduction table of the table build's exp (exp_tab)
-      if ((rc = upload_exp2_table(h->exp2_tab))) return bail(rc);
+      if ((rc = upload(h->ln_sw, sw.data(), (int64_t)sw.size(), d.ln_sw)) || (rc = upload_exp2_table(h->exp2_tab))) return rc;
       d.exp2_tab = h->exp2_tab.as<const double>();
     }
   }
-  if (c->cmb_mode != CF_CMB_NONE && (c->fde == CF_FDE_WCDM || c->fde == CF_FDE_CPL)) {
+  if (c->cmb_mode != CF_CMB_NONE && power_law_de) {
     // the dark-energy factor at the Gauss-Legendre nodes of the CMB distances goes through exp_tab / log10_tab (H_at_gl_node)
-    int rc;
-    if (!d.exp2_tab) {
-      if ((rc = upload_exp2_table(h->exp2_tab))) return bail(rc);
-      d.exp2_tab = h->exp2_tab.as<const double>();
-    }
-    if (!d.log10_tab) {
-      if ((rc = upload_log10_table(h->log10_tab))) return bail(rc);
-      d.log10_tab = h->log10_tab.p;
-    }
+    if ((!d.exp2_tab && (rc = upload_exp2_table(h->exp2_tab))) || (!d.log10_tab && (rc = upload_log10_table(h->log10_tab)))) return rc;
+    d.exp2_tab = h->exp2_tab.as<const double>();
+    d.log10_tab = h->log10_tab.p;
   }
-  if (c->n_cc > 0) {
-    int rc;
-    if ((rc = upload_vec(h->cc_z, c->cc_z, c->n_cc))) return bail(rc);
-    if ((rc = upload_vec(h->cc_h, c->cc_h, c->n_cc))) return bail(rc);
-    if ((rc = upload_vec(h->cc_inv_cov, c->cc_inv_cov, (int64_t)c->n_cc * c->n_cc))) return bail(rc);
-    d.cc_z = h->cc_z.as<const double>();
-    d.cc_h = h->cc_h.as<const double>();
-    d.cc_inv_cov = h->cc_inv_cov.as<const double>();
-  }
-  if (c->n_sn > 0 && c->sn_fixed_mu) {
-    int rc;
-    if ((rc = upload_vec(h->fixed_mu, c->sn_fixed_mu, c->n_sn))) return bail(rc);
-    d.sn_fixed_mu = h->fixed_mu.as<const double>();
-  }
-  if (c->n_sn > 0 && c->sn_lin_coef) {
-    int rc;
-    if ((rc = upload_vec(h->sn_lin, c->sn_lin_coef, c->n_sn))) return bail(rc);
-    d.sn_lin = h->sn_lin.as<const double>();
-  }
-  if (c->n_sn > 0 && c->sn_dir) {
-    int rc;
-    if ((rc = upload_vec(h->sn_dir, c->sn_dir, 3 * c->n_sn))) return bail(rc);
-    d.sn_dir = h->sn_dir.as<const double>();
-  }
-  if (c->cmb_mode != CF_CMB_NONE) {
-    int rc;
-    if ((rc = upload_vec(h->gl_x, c->gl_x, c->n_gl))) return bail(rc);
-    if ((rc = upload_vec(h->gl_w, c->gl_w, c->n_gl))) return bail(rc);
-    d.gl_x = h->gl_x.as<const double>();
-    d.gl_w = h->gl_w.as<const double>();
-  }
-  if (h->nonfinite.ensure(8)) return bail(CF_ERR_HIP);
-  if (hipMemset(h->nonfinite.p, 0, 8) != hipSuccess) return bail(fail(CF_ERR_HIP, "hipMemset failed"));
+  return 0;
+}
+
+// Cosmic chronometers, the SN block's optional per-SN arrays, the Gauss-Legendre nodes of the CMB distances.
+static int upload_cc_sn_extras_gl(const cf_desc* c, cf_handle* h) {
+  cf_dev_desc& d = h->d;
+  int rc;
+  if (c->n_cc > 0 && ((rc = upload(h->cc_z, c->cc_z, c->n_cc, d.cc_z)) || (rc = upload(h->cc_h, c->cc_h, c->n_cc, d.cc_h)) ||
+                      (rc = upload(h->cc_inv_cov, c->cc_inv_cov, (int64_t)c->n_cc * c->n_cc, d.cc_inv_cov))))
+    return rc;
+  if (c->n_sn > 0 && c->sn_fixed_mu && (rc = upload(h->fixed_mu, c->sn_fixed_mu, c->n_sn, d.sn_fixed_mu))) return rc;
+  if (c->n_sn > 0 && c->sn_lin_coef && (rc = upload(h->sn_lin, c->sn_lin_coef, c->n_sn, d.sn_lin))) return rc;
+  if (c->n_sn > 0 && c->sn_dir && (rc = upload(h->sn_dir, c->sn_dir, 3 * c->n_sn, d.sn_dir))) return rc;
+  if (c->cmb_mode != CF_CMB_NONE &&
+      ((rc = upload(h->gl_x, c->gl_x, c->n_gl, d.gl_x)) || (rc = upload(h->gl_w, c->gl_w, c->n_gl, d.gl_w))))
+    return rc;
+  return 0;
+}
+
+// The non-finite counter, and the prior / output epilogue's view of the descriptor: by value for finalize_kernel, through its
+// device copy for the solve kernels.
+static int upload_epilogue(cf_handle* h) {
+  const cf_dev_desc& d = h->d;
+  if (h->nonfinite.ensure(8)) return CF_ERR_HIP;
+  HIP_TRY(hipMemset(h->nonfinite.p, 0, 8));
   // the register path of walker_kernel's table build (chunk_shift == 3) reads its theta-independent tables without a
   // run-time fallback: a descriptor that needs one and does not carry it must never reach a launch
   if (d.chunk_shift == 3 && ((d.ez_model == CF_EZ_PHYSICAL_D && !d.nu_sw) ||
                              ((d.fde == CF_FDE_WCDM_D || d.fde == CF_FDE_CPL_D) && (!d.ln_sw || !d.exp2_tab))))
-    return bail(fail(CF_ERR_INVALID, "cf_create: internal: the table build's neutrino / ln(1 + z) tables are missing"));
-  // the prior / output epilogue's view of the descriptor: by value for finalize_kernel, through its device copy for the solve kernels
+    return fail(CF_ERR_INVALID, "cf_create: internal: the table build's neutrino / ln(1 + z) tables are missing");
   h->epi_host = epilogue_of(d);
-  if (h->epi.ensure(sizeof(cf_epilogue))) return bail(CF_ERR_HIP);
-  if (hipMemcpy(h->epi.p, &h->epi_host, sizeof(cf_epilogue), hipMemcpyHostToDevice) != hipSuccess)
-    return bail(fail(CF_ERR_HIP, "hipMemcpy of the epilogue block failed"));
+  return upload(h->epi, &h->epi_host, 1);
+}
+
+int create_one(const cf_desc* c, int device, HostPrep& prep, cf_handle** out) {
+  cf_handle* h = new cf_handle();
+  auto bail = [&](int code) { cf_destroy(h); return code; };
+  h->device = device;
+  DeviceScope on_device(h->device);
+  if (on_device.err != hipSuccess) return bail(fail(CF_ERR_HIP, "hipSetDevice failed"));
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, h->device) == hipSuccess) {
+    h->cu_count = prop.multiProcessorCount;
+    snprintf(h->arch, sizeof(h->arch), "%s", prop.gcnArchName);
+  }
+  if (strncmp(h->arch, "gfx950", 6) != 0)
+    return bail(fail(CF_ERR_UNSUPPORTED, std::string("cf_create: device is ") + h->arch + ", this library is built for gfx950 only"));
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(CF_ERR_HIP, "hipStreamCreate failed"));
+  fill_desc(c, h->d);
+  h->has_small_blocks = c->n_bao > 0 || c->cmb_mode != CF_CMB_NONE || c->n_cc > 0;
+  h->has_growth = c->n_fs8 > 0;
+  int rc;
+  if (c->n_sn > 0 && (rc = upload_sn(c, prep, h))) return bail(rc);
+  if ((rc = upload_bao_aux(c, h))) return bail(rc);
+  if (c->n_fs8 > 0 && (rc = upload_growth(c, h))) return bail(rc);
+  if ((rc = upload_grid_tables(c, h)) || (rc = upload_cc_sn_extras_gl(c, h)) || (rc = upload_epilogue(h))) return bail(rc);
   *out = h;
+  return CF_OK;
+}
+
+// cf_resid_set_chunk, cf_mock_set_chunk, cf_infl_set_chunk: rows per chunk of one of the three loops over the workspace.
+int set_chunk(cf_handle* h, int64_t cf_handle::*field, int64_t rows, const char* fn) {
+  if (!h) return fail(CF_ERR_INVALID, std::string(fn) + ": null handle");
+  if (rows < 0 || rows > CF_RESID_MAX_CHUNK) return fail(CF_ERR_INVALID, std::string(fn) + ": rows must be in 0..65536");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->*field = rows;
   return CF_OK;
 }
 
@@ -1675,9 +1457,9 @@ static int order_behind_last(cf_handle* h, hipStream_t st) {
 }
 
 // Launch one evaluation of W walkers, ordered on `st` (and behind the handle's previous evaluation, whatever stream that ran on).
-static int launch_path(cf_handle* h, const double* d_theta, int64_t W, double* d_out, int out_kind, hipStream_t st,
-                       double* dm_out, double* mucorr_out, double* blocks_out, double* bao_out,
-                       double* chi2_sn_out = nullptr, double* fs8_block_out = nullptr, double* fs8_theory_out = nullptr) {
+int launch_path(cf_handle* h, const double* d_theta, int64_t W, double* d_out, int out_kind, hipStream_t st, double* dm_out,
+                double* mucorr_out, double* blocks_out, double* bao_out, double* chi2_sn_out, double* fs8_block_out,
+                double* fs8_theory_out) {
   { int rc0 = order_behind_last(h, st); if (rc0) return rc0; }
   const bool timed = h->timing_slots && (h->eval_calls++ % h->timing_stride) == 0;
   const int slot = timed ? (int)(h->timed_calls % h->timing_slots) : 0;
@@ -2205,994 +1987,5 @@ extern "C" int cf_selftest_pack_host(const double* L, int64_t n, int64_t ld, con
   if (pack_default(L, n, ld, hp) != 0) return fail(CF_ERR_NOT_POSDEF, "cf_selftest_pack_host: bad pivot");
   *chi2_out = cf_pack_replay_host(hp, b);
   if (packed_bytes) *packed_bytes = (int64_t)(hp.frags.size() * sizeof(cf_d2));
-  return CF_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Quasar Hubble-diagram likelihoods (include/cosmofit.h: cf_create_quasar): an ordinary handle whose per-walker kernel is
-// cosmofit_quasar.hip's; the SN solve, the epilogue, the workspace, timing and the completion words are the handle's own.
-// ------------------------------------------------------------------------------------------------
-extern "C" int cf_create_quasar(const cf_desc* c, const cf_qsr_ext* e, cf_handle** out) {
-  if (!c || !e || !out) return fail(CF_ERR_INVALID, "cf_create_quasar: null argument");
-  *out = nullptr;
-  if (c->n_devices != 0) return fail(CF_ERR_UNSUPPORTED, "cf_create_quasar: a quasar handle lives on one device (n_devices must be 0)");
-  int rc = validate_desc(c);
-  if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(CF_ERR_NO_DEVICE, "cf_create_quasar: no HIP device visible (this library has no CPU path)");
-  if (c->device < 0 || c->device >= ndev) return fail(CF_ERR_INVALID, "cf_create_quasar: device ordinal out of range");
-  HostPrep prep;
-  cf_handle* h = nullptr;
-  if ((rc = create_one(c, c->device, prep, &h))) return rc;
-  {
-    DeviceScope on_device(h->device);
-    if (on_device.err != hipSuccess) rc = fail(CF_ERR_HIP, "hipSetDevice failed");
-    else rc = cf_qsr_prepare(c, e, h->d.n_ld, &h->qsr);
-  }
-  if (rc) {
-    const std::string keep = g_err;
-    cf_destroy(h);
-    return fail(rc, keep);
-  }
-  *out = h;
-  return CF_OK;
-}
-
-extern "C" int cf_qsr_eval_parts(cf_handle* h, const double* theta, int64_t W, double* chi2_blocks, double* mu_sn, double* mu_qsr,
-                                 double* bao_theory) {
-  if (!h || !theta) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: null argument");
-  if (!h->qsr) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: not a quasar handle (cf_create_quasar)");
-  if (W <= 0 || W > (1 << 20)) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: W out of range");
-  if (mu_sn && h->d.n_sn == 0) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: this likelihood has no SN block");
-  const int64_t nq = cf_qsr_n_qsr(h->qsr), nb = cf_qsr_n_bao(h->qsr), n = h->d.n_sn;
-  if (bao_theory && nb == 0) return fail(CF_ERR_INVALID, "cf_qsr_eval_parts: this likelihood has no BAO block");
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  int rc;
-  if ((rc = ensure_workspace(h, W))) return rc;
-  DevBuf parts, snb, ms, mq, bt;
-  if (parts.ensure((size_t)W * 3 * 8) || snb.ensure((size_t)W * 8)) return CF_ERR_HIP;
-  HIP_TRY(hipMemsetAsync(parts.p, 0, (size_t)W * 3 * 8, h->stream));
-  HIP_TRY(hipMemsetAsync(snb.p, 0, (size_t)W * 8, h->stream));
-  if (mu_sn && ms.ensure((size_t)W * n * 8)) return CF_ERR_HIP;
-  if (mu_qsr && mq.ensure((size_t)W * nq * 8)) return CF_ERR_HIP;
-  if (bao_theory && bt.ensure((size_t)W * nb * 8)) return CF_ERR_HIP;
-  HIP_TRY(hipMemcpyAsync(h->theta.p, theta, (size_t)W * h->d.ndim * 8, hipMemcpyHostToDevice, h->stream));
-  cf_qsr_set_outputs(h->qsr, parts.as<double>(), ms.as<double>(), mq.as<double>(), bt.as<double>());
-  rc = launch_path(h, h->theta.as<const double>(), W, h->out.as<double>(), CF_OUT_CHI2, h->stream, nullptr, nullptr, nullptr, nullptr,
-                   n > 0 ? snb.as<double>() : nullptr);
-  cf_qsr_set_outputs(h->qsr, nullptr, nullptr, nullptr, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (mu_sn) HIP_TRY(hipMemcpy(mu_sn, ms.p, (size_t)W * n * 8, hipMemcpyDeviceToHost));
-  if (mu_qsr) HIP_TRY(hipMemcpy(mu_qsr, mq.p, (size_t)W * nq * 8, hipMemcpyDeviceToHost));
-  if (bao_theory) HIP_TRY(hipMemcpy(bao_theory, bt.p, (size_t)W * nb * 8, hipMemcpyDeviceToHost));
-  if (chi2_blocks) {
-    std::vector<double> sn((size_t)W);
-    HIP_TRY(hipMemcpy(chi2_blocks, parts.p, (size_t)W * 3 * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sn.data(), snb.p, (size_t)W * 8, hipMemcpyDeviceToHost));
-    for (int64_t w = 0; w < W; ++w) chi2_blocks[3 * w] = sn[(size_t)w];
-  }
-  return CF_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Derived parameters and prediction curves of posterior samples (kernels and launchers: cosmofit_derived.hip)
-// ------------------------------------------------------------------------------------------------
-int cf_derived_launch(const cf_dev_desc& d, const cf_derived_kargs& a, const double* d_theta, int64_t S, double* d_out, hipStream_t st);
-int cf_curves_launch(const cf_dev_desc& d, const double* d_theta, int64_t S, int code, const double* d_z, int nz, double* d_out,
-                     hipStream_t st);
-
-static const char* dq_name(int code) {
-  switch (code) {
-    case CF_DQ_H0: return "H0";
-    case CF_DQ_H: return "h";
-    case CF_DQ_OM: return "Om";
-    case CF_DQ_OMH2: return "omh2";
-    case CF_DQ_OBH2: return "obh2";
-    case CF_DQ_OCH2: return "och2";
-    case CF_DQ_W0: return "w0";
-    case CF_DQ_WA: return "wa";
-    case CF_DQ_Q0: return "q0";
-    case CF_DQ_J0: return "j0";
-    case CF_DQ_S8: return "S8";
-    case CF_DQ_RD: return "rd";
-    case CF_DQ_Z_STAR: return "z_star";
-    case CF_DQ_R_DRAG: return "r_drag";
-    case CF_DQ_Z_DRAG: return "z_drag";
-    case CF_DQ_Z_EQ: return "z_eq";
-    case CF_DQ_H_AT: return "H@z";
-    case CF_DQ_RS_STAR: return "rs_star";
-    case CF_DQ_DM_STAR: return "DM_star";
-    case CF_DQ_THETA_STAR100: return "theta_star100";
-    case CF_DQ_R: return "R";
-    case CF_DQ_LA: return "lA";
-    default: return nullptr;
-  }
-}
-static const char* curve_name(int code) {
-  static const char* names[] = {"H", "DM", "DV_rd", "DM_rd", "DH_rd", "F_AP", "mu"};
-  return code >= CF_CURVE_H && code <= CF_CURVE_MU ? names[code] : nullptr;
-}
-
-// a slot the descriptor filled: a theta index, or a non-zero constant (an unused slot is {idx -1, fixed 0})
-static bool slot_present(const cf_dev_desc& d, int s) { return d.slot[s].idx >= 0 || d.slot[s].fixed != 0.0; }
-
-// What a quantity reads of the handle; the first thing that is missing, or nullptr.
-static const char* missing_h0(const cf_dev_desc& d) { return slot_present(d, CF_P_H0) ? nullptr : "an H0 slot"; }
-static const char* missing_wb_wc(const cf_dev_desc& d) {
-  if (!slot_present(d, CF_P_OBH2)) return "an obh2 slot";
-  if (!slot_present(d, CF_P_OCH2)) return "an och2 slot";
-  return nullptr;
-}
-static const char* missing_om(const cf_dev_desc& d) {
-  if (d.ez_model == CF_EZ_PHYSICAL) {
-    if (const char* m = missing_h0(d)) return m;
-    return missing_wb_wc(d);
-  }
-  if (!slot_present(d, CF_P_OM)) return "an Om slot";
-  return d.om_mode ? missing_h0(d) : nullptr;
-}
-static const char* missing_wm_drag(const cf_dev_desc& d) {  // wb and the matter density of the r_drag / z_drag fits
-  if (!slot_present(d, CF_P_OBH2)) return "an obh2 slot";
-  if (d.rd_wm_late) {
-    if (const char* m = missing_h0(d)) return m;
-    return slot_present(d, CF_P_OM) ? nullptr : "an Om slot";
-  }
-  return slot_present(d, CF_P_OCH2) ? nullptr : "an och2 slot";
-}
-static const char* missing_rd(const cf_dev_desc& d) {
-  if (d.rd_from_fit) return missing_wm_drag(d);
-  return slot_present(d, CF_P_RD) ? nullptr : "an r_d slot or the r_drag fit (CF_RD_FIT)";
-}
-
-static int derived_prepare(cf_handle* h, const int32_t* codes, const double* args, int32_t n_q, const cf_derived_consts* consts,
-                           cf_derived_kargs& a, const char* fn) {
-  const std::string F = std::string(fn) + ": ";
-  if (h->qsr) return fail(CF_ERR_UNSUPPORTED, F + "a quasar handle has no derived quantities");
-  if (!h->peers.empty()) return fail(CF_ERR_INVALID, F + "this handle spans several devices; use one handle per device");
-  if (!codes) return fail(CF_ERR_INVALID, F + "null argument");
-  if (n_q < 1 || n_q > CF_DQ_MAX) return fail(CF_ERR_INVALID, F + "n_q must be in 1.." + std::to_string(CF_DQ_MAX));
-  if (consts && consts->struct_size != (int32_t)sizeof(cf_derived_consts)) return fail(CF_ERR_INVALID, F + "cf_derived_consts.struct_size mismatch");
-  const cf_dev_desc& d = h->d;
-  memset(&a, 0, sizeof(a));
-  a.n_q = n_q;
-  for (int q = 0; q < n_q; ++q) {
-    const int code = codes[q];
-    const char* name = dq_name(code);
-    if (!name) return fail(CF_ERR_INVALID, F + "unknown quantity code " + std::to_string(code));
-    const char* miss = nullptr;
-    double arg = args ? args[q] : 0.0;
-    switch (code) {
-      case CF_DQ_H0: case CF_DQ_H: miss = missing_h0(d); break;
-      case CF_DQ_OM: case CF_DQ_Q0: case CF_DQ_J0: miss = missing_om(d); break;
-      case CF_DQ_OMH2:
-        miss = d.ez_model == CF_EZ_PHYSICAL ? missing_wb_wc(d) : (missing_h0(d) ? missing_h0(d) : missing_om(d));
-        break;
-      case CF_DQ_OBH2: miss = slot_present(d, CF_P_OBH2) ? nullptr : "an obh2 slot"; break;
-      case CF_DQ_OCH2: miss = slot_present(d, CF_P_OCH2) ? nullptr : "an och2 slot"; break;
-      case CF_DQ_W0: case CF_DQ_WA: break;
-      case CF_DQ_S8: miss = slot_present(d, CF_P_S8) ? missing_om(d) : "a sigma8 slot"; break;
-      case CF_DQ_RD:
-        miss = missing_rd(d);
-        if (d.rd_from_fit) a.need |= CF_DQ_NEED_RDFIT;
-        break;
-      case CF_DQ_Z_STAR:
-        miss = d.cmb_mode == CF_CMB_NONE ? "a compressed-CMB block (z_star coefficients)" : missing_wb_wc(d);
-        a.need |= CF_DQ_NEED_ZSTAR;
-        break;
-      case CF_DQ_R_DRAG:
-        miss = (d.rd_from_fit || (consts && consts->has_rdrag_fit)) ? missing_wm_drag(d) : "r_drag coefficients (CF_RD_FIT or cf_derived_consts.rdrag_fit)";
-        a.need |= CF_DQ_NEED_RDFIT;
-        break;
-      case CF_DQ_Z_DRAG:
-        miss = consts ? missing_wm_drag(d) : "cf_derived_consts.zdrag_fit";
-        a.need |= CF_DQ_NEED_ZDRAG;
-        break;
-      case CF_DQ_Z_EQ:
-        miss = missing_wb_wc(d);
-        if (!(arg > 0.0)) arg = consts ? consts->zeq_or_h2 : 0.0;
-        if (!miss && !(arg > 0.0 && std::isfinite(arg))) miss = "Omega_r h^2 > 0 (arg or cf_derived_consts.zeq_or_h2)";
-        break;
-      case CF_DQ_H_AT:
-        miss = missing_h0(d) ? missing_h0(d) : (std::isfinite(arg) ? nullptr : "a finite redshift");
-        break;
-      default:  // the Gauss-Legendre quantities
-        miss = (d.n_gl < 1 || !d.gl_x || !d.gl_w) ? "Gauss-Legendre nodes (a compressed-CMB block)"
-                                                  : (missing_h0(d) ? missing_h0(d) : missing_wb_wc(d));
-        a.need |= CF_DQ_NEED_GL | CF_DQ_NEED_ZSTAR;
-        break;
-    }
-    if (miss) return fail(CF_ERR_INVALID, F + name + " needs " + miss + ", which this handle lacks");
-    a.codes[q] = code;
-    a.args[q] = arg;
-  }
-  if (consts)
-    for (int i = 0; i < 10; ++i) a.zdrag_fit[i] = consts->zdrag_fit[i];
-  for (int i = 0; i < 11; ++i) a.rdrag_fit[i] = d.rd_from_fit ? d.rd_fit[i] : (consts && consts->has_rdrag_fit ? consts->rdrag_fit[i] : 0.0);
-  return CF_OK;
-}
-
-static int curves_check(cf_handle* h, int32_t code, int32_t nz, const char* fn) {
-  const std::string F = std::string(fn) + ": ";
-  if (h->qsr) return fail(CF_ERR_UNSUPPORTED, F + "a quasar handle has no prediction curves; use cf_qsr_eval_parts");
-  if (!h->peers.empty()) return fail(CF_ERR_INVALID, F + "this handle spans several devices; use one handle per device");
-  const char* name = curve_name(code);
-  if (!name) return fail(CF_ERR_INVALID, F + "unknown curve code " + std::to_string(code));
-  if (nz < 1 || nz > CF_CURVE_MAX_NZ) return fail(CF_ERR_INVALID, F + "nz must be in 1.." + std::to_string(CF_CURVE_MAX_NZ));
-  const cf_dev_desc& d = h->d;
-  const char* miss = missing_h0(d);
-  if (!miss && d.ez_model == CF_EZ_PHYSICAL) miss = missing_wb_wc(d);
-  if (!miss && d.ez_model != CF_EZ_PHYSICAL) miss = missing_om(d);
-  if (!miss && (code == CF_CURVE_DV_RD || code == CF_CURVE_DM_RD || code == CF_CURVE_DH_RD)) miss = missing_rd(d);
-  if (!miss && !d.bao_dh_exact && d.n_grid < 3 && (code == CF_CURVE_DV_RD || code == CF_CURVE_DH_RD || code == CF_CURVE_FAP))
-    miss = "n_grid >= 3 (PCHIP D_H)";
-  if (miss) return fail(CF_ERR_INVALID, F + name + " needs " + miss + ", which this handle lacks");
-  return CF_OK;
-}
-
-#define CF_DQ_MAX_ROWS (((int64_t)1 << 31) - 1)
-
-extern "C" int cf_derived_device(cf_handle* h, const double* d_theta, int64_t S, const int32_t* codes, const double* args, int32_t n_q,
-                                 const cf_derived_consts* consts, double* d_out, void* hip_stream) {
-  if (!h) return fail(CF_ERR_INVALID, "cf_derived_device: null argument");
-  cf_derived_kargs a;
-  int rc = derived_prepare(h, codes, args, n_q, consts, a, "cf_derived_device");
-  if (rc) return rc;
-  if (S < 0 || S > CF_DQ_MAX_ROWS) return fail(CF_ERR_INVALID, "cf_derived_device: S out of range");
-  if (S == 0) return CF_OK;
-  if (!d_theta || !d_out) return fail(CF_ERR_INVALID, "cf_derived_device: null argument");
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  return cf_derived_launch(h->d, a, d_theta, S, d_out, (hipStream_t)hip_stream);
-}
-
-extern "C" int cf_curves_device(cf_handle* h, const double* d_theta, int64_t S, int32_t code, const double* d_z, int32_t nz,
-                                double* d_out, void* hip_stream) {
-  if (!h) return fail(CF_ERR_INVALID, "cf_curves_device: null argument");
-  int rc = curves_check(h, code, nz, "cf_curves_device");
-  if (rc) return rc;
-  if (S < 0 || S > CF_DQ_MAX_ROWS) return fail(CF_ERR_INVALID, "cf_curves_device: S out of range");
-  if (S == 0) return CF_OK;
-  if (!d_theta || !d_z || !d_out) return fail(CF_ERR_INVALID, "cf_curves_device: null argument");
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  return cf_curves_launch(h->d, d_theta, S, code, d_z, nz, d_out, (hipStream_t)hip_stream);
-}
-
-// Host-buffer twins: rows in chunks through temporary device buffers on the handle's own stream.
-#define CF_DQ_HOST_CHUNK 65536
-
-extern "C" int cf_derived(cf_handle* h, const double* theta, int64_t S, const int32_t* codes, const double* args, int32_t n_q,
-                          const cf_derived_consts* consts, double* out) {
-  if (!h) return fail(CF_ERR_INVALID, "cf_derived: null argument");
-  cf_derived_kargs a;
-  int rc = derived_prepare(h, codes, args, n_q, consts, a, "cf_derived");
-  if (rc) return rc;
-  if (S < 0 || S > CF_DQ_MAX_ROWS) return fail(CF_ERR_INVALID, "cf_derived: S out of range");
-  if (S == 0) return CF_OK;
-  if (!theta || !out) return fail(CF_ERR_INVALID, "cf_derived: null argument");
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  RowStage rows(h->stream, std::min<int64_t>(S, CF_DQ_HOST_CHUNK));
-  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
-  double* dout = rows.out(out, (size_t)n_q * 8);
-  return rows.run(S, [&](int64_t, int64_t m) { return cf_derived_launch(h->d, a, dth, m, dout, h->stream); });
-}
-
-extern "C" int cf_curves(cf_handle* h, const double* theta, int64_t S, int32_t code, const double* z, int32_t nz, double* out) {
-  if (!h) return fail(CF_ERR_INVALID, "cf_curves: null argument");
-  int rc = curves_check(h, code, nz, "cf_curves");
-  if (rc) return rc;
-  if (S < 0 || S > CF_DQ_MAX_ROWS) return fail(CF_ERR_INVALID, "cf_curves: S out of range");
-  if (S == 0) return CF_OK;
-  if (!theta || !z || !out) return fail(CF_ERR_INVALID, "cf_curves: null argument");
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  RowStage rows(h->stream, std::min<int64_t>(S, std::max<int64_t>(1, CF_DQ_HOST_CHUNK * 16 / nz)));
-  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
-  double* dout = rows.out(out, (size_t)nz * 8);
-  DevBuf dz;
-  if (dz.ensure((size_t)nz * 8)) return CF_ERR_HIP;
-  HIP_TRY(hipMemcpyAsync(dz.p, z, (size_t)nz * 8, hipMemcpyHostToDevice, h->stream));
-  return rows.run(S, [&](int64_t, int64_t m) {
-    return cf_curves_launch(h->d, dth, m, code, dz.as<const double>(), nz, dout, h->stream);
-  });
-}
-
-// ------------------------------------------------------------------------------------------------
-// Fit report: residual statistics of every chain sample (kernels: cosmofit_resid.hip).  The residual rows come from the accessor
-// path of the likelihood (launch_path with a mu_corr buffer, as cf_eval_parts), one chunk of rows at a time into the handle's
-// workspace; the two kernels reduce each chunk behind it on the same stream.
-// ------------------------------------------------------------------------------------------------
-#define CF_RESID_MAX_ROWS (((int64_t)1 << 31) - 1)
-#define CF_RESID_MAX_CHUNK 65536
-
-// What cf_resid and cf_infl check alike (F: "<entry point>: ").  Their refusals of a quasar or multi-device handle differ in the
-// return code and their accumulator messages in the wording, so those stay with each.
-static int check_block(const std::string& F, int64_t n_sn, int32_t n_bao, int32_t block) {
-  if (block != CF_RB_SN && block != CF_RB_BAO) return fail(CF_ERR_INVALID, F + "block must be CF_RB_SN or CF_RB_BAO");
-  if (block == CF_RB_SN && n_sn <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no SN block");
-  if (block == CF_RB_BAO && n_bao <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no BAO block");
-  return CF_OK;
-}
-static int check_rows_thresholds(const std::string& F, int64_t S, const double* thresholds, int32_t n_thr) {
-  if (S < 0 || S > CF_RESID_MAX_ROWS) return fail(CF_ERR_INVALID, F + "S out of range");
-  if (n_thr < 0 || n_thr > CF_RESID_MAX_THR) return fail(CF_ERR_INVALID, F + "n_thr must be in 0..4");
-  if (n_thr > 0 && !thresholds) return fail(CF_ERR_INVALID, F + "null thresholds");
-  for (int k = 0; k < n_thr; ++k)
-    if (!std::isfinite(thresholds[k]) || thresholds[k] < 0.0) return fail(CF_ERR_INVALID, F + "thresholds must be finite and >= 0");
-  return CF_OK;
-}
-static bool acc_lacks_an_array(const cf_resid_acc* acc, int32_t n_thr) {
-  return !acc->w_sum || !acc->mean || !acc->m2 || !acc->n_used || !acc->n_skipped || (n_thr > 0 && !acc->exceed);
-}
-
-extern "C" int cf_resid_check_args(int64_t n_sn, int32_t n_bao, int32_t is_quasar, int32_t n_devices, const void* theta, int64_t S,
-                                   int32_t block, const double* thresholds, int32_t n_thr, const void* sample, const void* chi2_blocks,
-                                   const cf_resid_acc* acc) {
-  const std::string F = "cf_resid: ";
-  int rc;
-  if (is_quasar) return fail(CF_ERR_UNSUPPORTED, F + "a quasar handle has no accessor path to take the residuals from");
-  if (n_devices > 1) return fail(CF_ERR_UNSUPPORTED, F + "this handle spans several devices; use one handle per device");
-  if ((rc = check_block(F, n_sn, n_bao, block))) return rc;
-  if ((rc = check_rows_thresholds(F, S, thresholds, n_thr))) return rc;
-  if (!sample && !chi2_blocks && !acc) return fail(CF_ERR_INVALID, F + "no output requested");
-  if (acc) {
-    const int64_t n = block == CF_RB_SN ? n_sn : n_bao;
-    if (acc->struct_size != (int32_t)sizeof(cf_resid_acc)) return fail(CF_ERR_INVALID, F + "cf_resid_acc.struct_size mismatch");
-    if (acc->n != n) return fail(CF_ERR_INVALID, F + "cf_resid_acc.n is not the number of data of the block");
-    if (acc->n_thr != n_thr) return fail(CF_ERR_INVALID, F + "cf_resid_acc.n_thr differs from n_thr");
-    if (acc_lacks_an_array(acc, n_thr)) return fail(CF_ERR_INVALID, F + "null array in cf_resid_acc");
-  }
-  if (S > 0 && !theta) return fail(CF_ERR_INVALID, F + "null theta");
-  return CF_OK;
-}
-
-static int resid_check(cf_handle* h, const void* theta, int64_t S, int32_t block, const double* thresholds, int32_t n_thr,
-                       const void* sample, const void* chi2_blocks, const cf_resid_acc* acc) {
-  if (!h) return fail(CF_ERR_INVALID, "cf_resid: null handle");
-  return cf_resid_check_args(h->d.n_sn, h->d.n_bao, h->qsr ? 1 : 0, 1 + (int32_t)h->peers.size(), theta, S, block, thresholds, n_thr,
-                             sample, chi2_blocks, acc);
-}
-
-extern "C" int cf_resid_sigma(cf_handle* h, int32_t block, double* out) {
-  if (!h || !out) return fail(CF_ERR_INVALID, "cf_resid_sigma: null argument");
-  if (block != CF_RB_SN && block != CF_RB_BAO) return fail(CF_ERR_INVALID, "cf_resid_sigma: block must be CF_RB_SN or CF_RB_BAO");
-  const std::vector<double>& s = block == CF_RB_SN ? h->sigma_sn_host : h->sigma_bao_host;
-  if (h->qsr || s.empty()) return fail(CF_ERR_INVALID, "cf_resid_sigma: this likelihood has no such block");
-  memcpy(out, s.data(), s.size() * 8);
-  return CF_OK;
-}
-
-// cf_resid_set_chunk, cf_mock_set_chunk, cf_infl_set_chunk: rows per chunk of one of the three loops over the workspace.
-static int set_chunk(cf_handle* h, int64_t cf_handle::*field, int64_t rows, const char* fn) {
-  if (!h) return fail(CF_ERR_INVALID, std::string(fn) + ": null handle");
-  if (rows < 0 || rows > CF_RESID_MAX_CHUNK) return fail(CF_ERR_INVALID, std::string(fn) + ": rows must be in 0..65536");
-  std::lock_guard<std::mutex> lk(h->mu);
-  h->*field = rows;
-  return CF_OK;
-}
-
-extern "C" int cf_resid_set_chunk(cf_handle* h, int64_t rows) { return set_chunk(h, &cf_handle::resid_chunk, rows, "cf_resid_set_chunk"); }
-
-// Buffers for chunks of `rows` rows and the device copy of sigma.  Growing frees buffers an evaluation on a caller's stream may
-// still use: synchronise first, as ensure_workspace does.
-static int resid_prepare(const HandleScope& hs, int64_t rows) {
-  cf_handle* const h = hs.h;
-  if (!h->sigma_uploaded) {
-    int rc;
-    if (!h->sigma_sn_host.empty() && (rc = upload_vec(h->sigma_sn, h->sigma_sn_host.data(), (int64_t)h->sigma_sn_host.size()))) return rc;
-    if (!h->sigma_bao_host.empty() && (rc = upload_vec(h->sigma_bao, h->sigma_bao_host.data(), (int64_t)h->sigma_bao_host.size())))
-      return rc;
-    h->sigma_uploaded = true;
-  }
-  if (rows <= h->resid_rows) return 0;
-  HIP_TRY(hipDeviceSynchronize());
-  const int64_t n = h->d.n_sn, nb = h->d.n_bao;
-  if (n > 0 && h->r_mc.ensure((size_t)rows * n * 8)) return CF_ERR_HIP;
-  if (nb > 0 && h->r_bt.ensure((size_t)rows * nb * 8)) return CF_ERR_HIP;
-  if (h->r_blk.ensure((size_t)rows * 8 * 8) || h->r_snb.ensure((size_t)rows * 8) || h->r_fsb.ensure((size_t)rows * 8)) return CF_ERR_HIP;
-  h->resid_rows = rows;
-  return 0;
-}
-
-// Arguments checked.  Device pointers throughout.
-static int resid_run(const HandleScope& hs, const double* d_theta, int64_t S, const double* d_w, int32_t block,
-                     const double* thresholds, int32_t n_thr, double* d_sample, double* d_chi2_blocks, const cf_resid_acc* acc,
-                     hipStream_t st) {
-  cf_handle* const h = hs.h;
-  int rc;
-  const int64_t chunk = std::min<int64_t>(S, h->resid_chunk > 0 ? h->resid_chunk : CF_RESID_CHUNK);
-  if ((rc = ensure_workspace(h, chunk))) return rc;
-  if ((rc = resid_prepare(hs, chunk))) return rc;
-  const cf_dev_desc& d = h->d;
-  const bool want_blocks = d_chi2_blocks != nullptr;
-  cf_resid_src src{};
-  if (block == CF_RB_SN) {
-    src.rows = h->delta.as<const double>();
-    src.data = d.obs;
-    src.mu_corr = h->r_mc.as<const double>();
-    src.sigma = h->sigma_sn.as<const double>();
-    src.pitch = d.n_ld;
-    src.n = d.n_sn;
-    src.bao = 0;
-  } else {
-    src.rows = h->r_bt.as<const double>();
-    src.data = d.bao_val;
-    src.mu_corr = nullptr;
-    src.sigma = h->sigma_bao.as<const double>();
-    src.pitch = d.n_bao;
-    src.n = d.n_bao;
-    src.bao = 1;
-  }
-  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-    const int64_t m = std::min(chunk, S - s0);
-    if (want_blocks) {  // a block the likelihood lacks keeps 0, as in cf_eval_parts
-      HIP_TRY(hipMemsetAsync(h->r_snb.p, 0, (size_t)m * 8, st));
-      HIP_TRY(hipMemsetAsync(h->r_fsb.p, 0, (size_t)m * 8, st));
-      HIP_TRY(hipMemsetAsync(h->r_blk.p, 0, (size_t)m * 8 * 8, st));
-    }
-    // a mu_corr buffer selects the accessor form of the per-walker kernel (the reference's exact sequence, rows in row layout)
-    if ((rc = launch_path(h, d_theta + s0 * d.ndim, m, h->out.as<double>(), CF_OUT_CHI2, st, nullptr,
-                          d.n_sn > 0 ? h->r_mc.as<double>() : nullptr, want_blocks ? h->r_blk.as<double>() : nullptr,
-                          d.n_bao > 0 ? h->r_bt.as<double>() : nullptr, want_blocks ? h->r_snb.as<double>() : nullptr,
-                          want_blocks ? h->r_fsb.as<double>() : nullptr, nullptr)))
-      return rc;
-    cf_resid_blocks blk{h->r_snb.as<const double>(), h->r_blk.as<const double>(), h->r_fsb.as<const double>(),
-                        want_blocks ? d_chi2_blocks + 10 * s0 : nullptr};
-    if ((rc = cf_resid_launch(src, m, d_sample ? d_sample + (int64_t)CF_RS_NCOL * s0 : nullptr, blk, d_w ? d_w + s0 : nullptr, thresholds,
-                              n_thr, acc, st)))
-      return rc;
-  }
-  return CF_OK;
-}
-
-extern "C" int cf_resid_device(cf_handle* h, const double* d_theta, int64_t S, const double* d_w, int32_t block, const double* thresholds,
-                               int32_t n_thr, double* d_sample, double* d_chi2_blocks, cf_resid_acc* acc, void* hip_stream) {
-  int rc = resid_check(h, d_theta, S, block, thresholds, n_thr, d_sample, d_chi2_blocks, acc);
-  if (rc) return rc;
-  if (S == 0) return CF_OK;
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  return resid_run(hs, d_theta, S, d_w, block, thresholds, n_thr, d_sample, d_chi2_blocks, acc, (hipStream_t)hip_stream);
-}
-
-// The device twin of a host cf_resid_acc: up once, continued piece by piece on the device, down at the end.
-struct HostAccTwin {
-  DevBuf w, mean, m2, ex, used, skip;
-  cf_resid_acc dev{};
-  cf_resid_acc* host = nullptr;
-  int up(cf_resid_acc* acc, hipStream_t st) {
-    host = acc;
-    if (!acc) return 0;
-    const size_t nb = (size_t)acc->n * 8, ne = nb * (size_t)acc->n_thr;
-    dev = *acc;
-    if (w.ensure(nb) || mean.ensure(nb) || m2.ensure(nb) || used.ensure(nb) || skip.ensure(nb) || (ne && ex.ensure(ne))) return CF_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(w.p, acc->w_sum, nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(mean.p, acc->mean, nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m2.p, acc->m2, nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(used.p, acc->n_used, nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(skip.p, acc->n_skipped, nb, hipMemcpyHostToDevice, st));
-    if (ne) HIP_TRY(hipMemcpyAsync(ex.p, acc->exceed, ne, hipMemcpyHostToDevice, st));
-    dev.w_sum = w.as<double>(); dev.mean = mean.as<double>(); dev.m2 = m2.as<double>(); dev.exceed = ex.as<double>();
-    dev.n_used = used.as<int64_t>(); dev.n_skipped = skip.as<int64_t>();
-    return 0;
-  }
-  int down() {
-    if (!host) return 0;
-    const size_t nb = (size_t)host->n * 8, ne = nb * (size_t)host->n_thr;
-    HIP_TRY(hipMemcpy(host->w_sum, w.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(host->mean, mean.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(host->m2, m2.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(host->n_used, used.p, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(host->n_skipped, skip.p, nb, hipMemcpyDeviceToHost));
-    if (ne) HIP_TRY(hipMemcpy(host->exceed, ex.p, ne, hipMemcpyDeviceToHost));
-    return 0;
-  }
-  const cf_resid_acc* ptr() const { return host ? &dev : nullptr; }
-};
-
-// Host-buffer twin: rows in pieces through temporary device buffers on the handle's own stream; the accumulator goes to the
-// device once, is continued there piece by piece, and comes back at the end.
-#define CF_RESID_HOST_PIECE 65536
-
-extern "C" int cf_resid(cf_handle* h, const double* theta, int64_t S, const double* w, int32_t block, const double* thresholds,
-                        int32_t n_thr, double* sample, double* chi2_blocks, cf_resid_acc* acc) {
-  int rc = resid_check(h, theta, S, block, thresholds, n_thr, sample, chi2_blocks, acc);
-  if (rc) return rc;
-  if (S == 0) return CF_OK;
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  RowStage rows(h->stream, std::min<int64_t>(S, CF_RESID_HOST_PIECE));
-  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
-  const double* dw = rows.in(w, 8);
-  double* ds = rows.out(sample, (size_t)CF_RS_NCOL * 8);
-  double* db = rows.out(chi2_blocks, 10 * 8);
-  HostAccTwin dacc;
-  if ((rc = dacc.up(acc, h->stream))) return rc;
-  if ((rc = rows.run(S, [&](int64_t, int64_t m) {
-         return resid_run(hs, dth, m, dw, block, thresholds, n_thr, ds, db, dacc.ptr(), h->stream);
-       })))
-    return rc;
-  return dacc.down();
-}
-
-// ------------------------------------------------------------------------------------------------
-// Mock-data ensembles: the likelihood on per-row shifted data (kernels: cosmofit_mock.hip).  The residual rows come from the
-// accessor path, one chunk of rows at a time into the handle's workspace, exactly as resid_run gets them (the CMB theory vector
-// is columns 2..4 of r_blk); the likelihood's own value for out_kind lands in h->out and mock_shift_kernel adds the shift
-// behind it on the same stream.
-// ------------------------------------------------------------------------------------------------
-extern "C" int cf_mock_check_args(int64_t n_sn, int32_t n_bao, int32_t has_cmb, int32_t is_quasar, int32_t n_devices,
-                                  const cf_mock_set* set, const void* theta, int64_t S, const void* mock, int32_t out_kind,
-                                  const void* out) {
-  const std::string F = "cf_mock_eval: ";
-  if (is_quasar) return fail(CF_ERR_UNSUPPORTED, F + "a quasar handle has no accessor path to take the residuals from");
-  if (n_devices > 1) return fail(CF_ERR_UNSUPPORTED, F + "this handle spans several devices; use one handle per device");
-  if (!set) return fail(CF_ERR_INVALID, F + "null cf_mock_set");
-  if (set->struct_size != (int32_t)sizeof(cf_mock_set)) return fail(CF_ERR_INVALID, F + "cf_mock_set.struct_size mismatch");
-  if (set->n_mocks < 1) return fail(CF_ERR_INVALID, F + "n_mocks must be >= 1");
-  if (set->n_sn != 0 && n_sn <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no SN block");
-  if (set->n_bao != 0 && n_bao <= 0) return fail(CF_ERR_INVALID, F + "this likelihood has no BAO block");
-  if (set->n_cmb != 0 && !has_cmb) return fail(CF_ERR_INVALID, F + "this likelihood has no CMB block");
-  if (set->n_sn != 0 && (int64_t)set->n_sn != n_sn) return fail(CF_ERR_INVALID, F + "cf_mock_set.n_sn is neither 0 nor the handle's n_sn");
-  if (set->n_bao != 0 && set->n_bao != n_bao) return fail(CF_ERR_INVALID, F + "cf_mock_set.n_bao is neither 0 nor the handle's n_bao");
-  if (set->n_cmb != 0 && set->n_cmb != 3) return fail(CF_ERR_INVALID, F + "cf_mock_set.n_cmb must be 0 or 3");
-  if (set->n_sn == 0 && set->n_bao == 0 && set->n_cmb == 0) return fail(CF_ERR_INVALID, F + "no shifted block");
-  if ((set->n_sn != 0 && !set->g_sn) || (set->n_bao != 0 && !set->g_bao) || (set->n_cmb != 0 && !set->g_cmb) || !set->c)
-    return fail(CF_ERR_INVALID, F + "null array in cf_mock_set");
-  if (out_kind < CF_OUT_CHI2 || out_kind > CF_OUT_LOGP) return fail(CF_ERR_INVALID, F + "bad out_kind");
-  if (S < 0 || S > CF_RESID_MAX_ROWS) return fail(CF_ERR_INVALID, F + "S out of range");
-  if (S > 0 && (!theta || !mock || !out)) return fail(CF_ERR_INVALID, F + "null theta, mock or out");
-  return CF_OK;
-}
-
-static int mock_check(cf_handle* h, const cf_mock_set* set, const void* theta, int64_t S, const void* mock, int32_t out_kind,
-                      const void* out) {
-  if (!h) return fail(CF_ERR_INVALID, "cf_mock_eval: null handle");
-  return cf_mock_check_args(h->d.n_sn, h->d.n_bao, h->d.cmb_mode != 0 ? 1 : 0, h->qsr ? 1 : 0, 1 + (int32_t)h->peers.size(), set, theta,
-                            S, mock, out_kind, out);
-}
-
-extern "C" int cf_mock_set_chunk(cf_handle* h, int64_t rows) { return set_chunk(h, &cf_handle::mock_chunk, rows, "cf_mock_set_chunk"); }
-
-// Arguments checked.  Device pointers throughout (the set's arrays too).
-static int mock_run(const HandleScope& hs, const cf_mock_set& set, const double* d_theta, int64_t S, const int32_t* d_mock,
-                    int32_t out_kind, double* d_out, double* d_cross, hipStream_t st) {
-  cf_handle* const h = hs.h;
-  int rc;
-  const int64_t chunk = std::min<int64_t>(S, h->mock_chunk > 0 ? h->mock_chunk : CF_MOCK_CHUNK);
-  if ((rc = ensure_workspace(h, chunk))) return rc;
-  if ((rc = resid_prepare(hs, chunk))) return rc;
-  const cf_dev_desc& d = h->d;
-  cf_mock_args a{};
-  a.sn_rows = h->delta.as<const double>();
-  a.sn_pitch = d.n_ld;
-  a.bao_theory = h->r_bt.as<const double>();
-  a.bao_val = d.bao_val;
-  a.b8 = h->r_blk.as<const double>();
-  a.base = h->out.as<const double>();
-  a.g_sn = set.g_sn; a.g_bao = set.g_bao; a.g_cmb = set.g_cmb; a.c = set.c;
-  for (int i = 0; i < 3; ++i) a.cmb_prior[i] = d.cmb_prior[i];
-  a.n_sn = set.n_sn; a.n_bao = set.n_bao; a.n_cmb = set.n_cmb; a.n_mocks = set.n_mocks;
-  a.out_kind = out_kind;
-  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-    const int64_t m = std::min(chunk, S - s0);
-    // a mu_corr buffer selects the accessor form of the per-walker kernel (residual rows in row layout), as in resid_run
-    if ((rc = launch_path(h, d_theta + s0 * d.ndim, m, h->out.as<double>(), out_kind, st, nullptr,
-                          d.n_sn > 0 ? h->r_mc.as<double>() : nullptr, h->r_blk.as<double>(),
-                          d.n_bao > 0 ? h->r_bt.as<double>() : nullptr)))
-      return rc;
-    if ((rc = cf_mock_launch(a, m, d_mock + s0, d_out + s0, d_cross ? d_cross + 3 * s0 : nullptr, st))) return rc;
-  }
-  return CF_OK;
-}
-
-extern "C" int cf_mock_eval_device(cf_handle* h, const cf_mock_set* set, const double* d_theta, int64_t S, const int32_t* d_mock,
-                                   int32_t out_kind, double* d_out, double* d_cross, void* hip_stream) {
-  int rc = mock_check(h, set, d_theta, S, d_mock, out_kind, d_out);
-  if (rc) return rc;
-  if (S == 0) return CF_OK;
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  return mock_run(hs, *set, d_theta, S, d_mock, out_kind, d_out, d_cross, (hipStream_t)hip_stream);
-}
-
-// Host-buffer twin: the set goes to the device once, the rows in pieces through temporary device buffers on the handle's stream.
-extern "C" int cf_mock_eval(cf_handle* h, const cf_mock_set* set, const double* theta, int64_t S, const int32_t* mock,
-                            int32_t out_kind, double* out, double* cross) {
-  int rc = mock_check(h, set, theta, S, mock, out_kind, out);
-  if (rc) return rc;
-  if (S == 0) return CF_OK;
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  const int64_t K = set->n_mocks;
-  DevBuf gs, gb, gc, cc;
-  cf_mock_set dset = *set;
-  if (set->n_sn) {
-    if (gs.ensure((size_t)K * set->n_sn * 8)) return CF_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(gs.p, set->g_sn, (size_t)K * set->n_sn * 8, hipMemcpyHostToDevice, h->stream));
-    dset.g_sn = gs.as<const double>();
-  }
-  if (set->n_bao) {
-    if (gb.ensure((size_t)K * set->n_bao * 8)) return CF_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(gb.p, set->g_bao, (size_t)K * set->n_bao * 8, hipMemcpyHostToDevice, h->stream));
-    dset.g_bao = gb.as<const double>();
-  }
-  if (set->n_cmb) {
-    if (gc.ensure((size_t)K * 3 * 8)) return CF_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(gc.p, set->g_cmb, (size_t)K * 3 * 8, hipMemcpyHostToDevice, h->stream));
-    dset.g_cmb = gc.as<const double>();
-  }
-  if (cc.ensure((size_t)K * 8)) return CF_ERR_HIP;
-  HIP_TRY(hipMemcpyAsync(cc.p, set->c, (size_t)K * 8, hipMemcpyHostToDevice, h->stream));
-  dset.c = cc.as<const double>();
-  RowStage rows(h->stream, std::min<int64_t>(S, CF_RESID_HOST_PIECE));
-  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
-  const int32_t* dmk = rows.in(mock, 4);
-  double* dout = rows.out(out, 8);
-  double* dcr = rows.out(cross, 3 * 8);
-  return rows.run(S, [&](int64_t, int64_t m) { return mock_run(hs, dset, dth, m, dmk, out_kind, dout, dcr, h->stream); });
-}
-
-// ------------------------------------------------------------------------------------------------
-// Attribution and leave-one-out residuals: which data carry a chi^2 (kernels: cosmofit_infl.hip).  Everything follows from
-// g = K r with K = C^-1: the precision matrix is formed once on the host (cf_prec), the residual rows come from the accessor
-// path one chunk at a time exactly as resid_run gets them, prec_gemm_kernel forms g behind them on the same stream,
-// infl_row_kernel the per-row quantities, and the fit report's resid_datum_kernel continues the per-datum accumulators over the
-// z and contrib rows (a unit sigma, so its thresholds are in sigmas).
-// ------------------------------------------------------------------------------------------------
-#define CF_PREC_MAX_N 32768
-
-struct cf_prec {
-  int64_t n = 0, kp = 0;  // kp: row pitch of K on the device, n rounded up to 16 (zero in the padding)
-  int device = 0;
-  DevBuf K, kdiag, inv_sqrt_kdiag, ones;
-  std::vector<double> kdiag_host;
-};
-
-static unsigned prec_threads(int64_t n) {
-  unsigned nt = std::thread::hardware_concurrency();
-  nt = nt == 0 ? 1 : (nt > 16 ? 16 : nt);
-  return n < 256 ? 1 : nt;
-}
-
-template <class F>
-static void prec_parallel(unsigned nt, F work) {
-  if (nt == 1) {
-    work(0u);
-    return;
-  }
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nt; ++t) th.emplace_back(work, t);
-  for (auto& x : th) x.join();
-}
-
-// s + c carries the running sum: c collects what each addition rounds away (Knuth's TwoSum, branch-free)
-static inline void prec_add(long double& s, long double& c, long double p) {
-  const long double t = s + p, z = t - s;
-  c += (s - (t - z)) + (p - z);
-  s = t;
-}
-
-// Column j of Linv in extended precision, col[j .. n-1] indexed by the row: the forward substitution of cf_invert_lower
-// (cf_pack.h) with compensated sums.  The plain recurrence loses sqrt(n) cond(L) 2^-64 of an entry, which on the Pantheon+-like
-// covariances (cond(L) of a few hundred) is several units of the double the precision matrix is rounded to.
-static void prec_inverse_column(const double* L, int64_t n, int64_t ld, int64_t j, long double* col) {
-  col[j] = 1.0L / (long double)L[j * ld + j];
-  for (int64_t i = j + 1; i < n; ++i) {
-    const double* row = L + i * ld;
-    long double s0 = 0.0L, c0 = 0.0L, s1 = 0.0L, c1 = 0.0L;
-    int64_t k = j;
-    for (; k + 1 < i; k += 2) {
-      prec_add(s0, c0, (long double)row[k] * col[k]);
-      prec_add(s1, c1, (long double)row[k + 1] * col[k + 1]);
-    }
-    if (k < i) prec_add(s0, c0, (long double)row[k] * col[k]);
-    prec_add(s0, c0, s1);
-    col[i] = -(s0 + (c0 + c1)) / (long double)row[i];
-  }
-}
-
-// K = Linv^T Linv [n x n] of the lower-triangular factor L, every product and sum in `long double`: the columns of Linv stay in
-// extended precision (column j packed as its n - j entries from the diagonal down), K_ij = sum_{k >= max(i, j)} Linv_ki Linv_kj
-// in four accumulation chains, and the stored double is the one rounding of that sum.
-static void prec_from_factor(const double* L, int64_t n, int64_t ld, std::vector<double>& K) {
-  std::vector<size_t> off((size_t)n + 1, 0);
-  for (int64_t j = 0; j < n; ++j) off[j + 1] = off[j] + (size_t)(n - j);
-  std::vector<long double> X(off[n]);
-  const unsigned nt = prec_threads(n);
-  // interleaved columns / rows: neighbours cost the same
-  prec_parallel(nt, [&](unsigned t) {
-    for (int64_t j = t; j < n; j += nt) prec_inverse_column(L, n, ld, j, X.data() + off[j] - j);
-  });
-  K.assign((size_t)n * n, 0.0);
-  prec_parallel(nt, [&](unsigned t) {
-    for (int64_t i = t; i < n; i += nt) {
-      const long double* xi = X.data() + off[i] - i;  // indexed by the row k >= i
-      for (int64_t j = 0; j <= i; ++j) {
-        const long double* xj = X.data() + off[j] - j;
-        long double a0 = 0.0L, a1 = 0.0L, a2 = 0.0L, a3 = 0.0L;
-        int64_t k = i;
-        for (; k + 3 < n; k += 4) {
-          a0 += xi[k] * xj[k];
-          a1 += xi[k + 1] * xj[k + 1];
-          a2 += xi[k + 2] * xj[k + 2];
-          a3 += xi[k + 3] * xj[k + 3];
-        }
-        for (; k < n; ++k) a0 += xi[k] * xj[k];
-        const double v = (double)((a0 + a1) + (a2 + a3));
-        K[(size_t)i * n + j] = v;
-        K[(size_t)j * n + i] = v;
-      }
-    }
-  });
-}
-
-static int prec_check_shape(const char* fn, const void* a, int64_t n, int64_t ld) {
-  const std::string F = std::string(fn) + ": ";
-  if (!a) return fail(CF_ERR_INVALID, F + "null matrix");
-  if (n < 1 || n > CF_PREC_MAX_N) return fail(CF_ERR_INVALID, F + "n must be in 1..32768");
-  if (ld < n) return fail(CF_ERR_INVALID, F + "ld < n");
-  return CF_OK;
-}
-
-static int prec_check_factor(const char* fn, const double* L, int64_t n, int64_t ld) {
-  int rc = prec_check_shape(fn, L, n, ld);
-  if (rc) return rc;
-  for (int64_t i = 0; i < n; ++i)
-    if (!(L[i * ld + i] > 0.0) || !std::isfinite(L[i * ld + i])) return fail(CF_ERR_NOT_POSDEF, std::string(fn) + ": bad pivot");
-  return CF_OK;
-}
-
-extern "C" int cf_selftest_prec_host(const double* L, int64_t n, int64_t ld, double* K_out, double* kdiag_out) {
-  int rc = prec_check_factor("cf_selftest_prec_host", L, n, ld);
-  if (rc) return rc;
-  std::vector<double> K;
-  prec_from_factor(L, n, ld, K);
-  if (K_out) memcpy(K_out, K.data(), K.size() * 8);
-  if (kdiag_out)
-    for (int64_t i = 0; i < n; ++i) kdiag_out[i] = K[(size_t)i * n + i];
-  return CF_OK;
-}
-
-// K [n x n] to the device: zero-padded to pitch kp, its diagonal, 1 / sqrt(diagonal) (0 for a datum the likelihood ignores) and
-// the unit sigma the accumulators of the z and contrib rows divide by.
-static int prec_upload(const char* fn, const std::vector<double>& K, int64_t n, int32_t device, cf_prec** out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(CF_ERR_NO_DEVICE, std::string(fn) + ": no HIP device visible (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(CF_ERR_INVALID, std::string(fn) + ": device ordinal out of range");
-  std::unique_ptr<cf_prec> p(new cf_prec());
-  p->n = n;
-  p->kp = (n + 15) / 16 * 16;
-  p->device = device;
-  std::vector<double> Kp((size_t)p->kp * p->kp, 0.0), isk((size_t)n), ones((size_t)n, 1.0);
-  p->kdiag_host.resize((size_t)n);
-  for (int64_t i = 0; i < n; ++i) {
-    memcpy(&Kp[(size_t)i * p->kp], &K[(size_t)i * n], (size_t)n * 8);
-    const double kd = K[(size_t)i * n + i];
-    p->kdiag_host[i] = kd;
-    isk[i] = kd > 0.0 ? (double)(1.0L / sqrtl((long double)kd)) : 0.0;
-  }
-  DeviceScope on_device(device);
-  HIP_TRY(on_device.err);
-  int rc;
-  if ((rc = upload_vec(p->K, Kp.data(), (int64_t)Kp.size()))) return rc;
-  if ((rc = upload_vec(p->kdiag, p->kdiag_host.data(), n))) return rc;
-  if ((rc = upload_vec(p->inv_sqrt_kdiag, isk.data(), n))) return rc;
-  if ((rc = upload_vec(p->ones, ones.data(), n))) return rc;
-  *out = p.release();
-  return CF_OK;
-}
-
-extern "C" int cf_prec_create(const double* L, int64_t n, int64_t ld, int32_t device, cf_prec** out) {
-  if (!out) return fail(CF_ERR_INVALID, "cf_prec_create: null argument");
-  *out = nullptr;
-  int rc = prec_check_factor("cf_prec_create", L, n, ld);
-  if (rc) return rc;
-  std::vector<double> K;
-  prec_from_factor(L, n, ld, K);
-  return prec_upload("cf_prec_create", K, n, device, out);
-}
-
-extern "C" int cf_prec_create_inv(const double* inv_cov, int64_t n, int64_t ld, int32_t device, cf_prec** out) {
-  if (!out) return fail(CF_ERR_INVALID, "cf_prec_create_inv: null argument");
-  *out = nullptr;
-  int rc = prec_check_shape("cf_prec_create_inv", inv_cov, n, ld);
-  if (rc) return rc;
-  std::vector<double> K((size_t)n * n);
-  for (int64_t i = 0; i < n; ++i)
-    for (int64_t j = 0; j < n; ++j) {
-      const double v = 0.5 * (inv_cov[i * ld + j] + inv_cov[j * ld + i]);
-      if (!std::isfinite(v) || (i == j && v < 0.0))
-        return fail(CF_ERR_NOT_POSDEF, "cf_prec_create_inv: a non-finite entry or a negative diagonal entry");
-      K[(size_t)i * n + j] = v;
-    }
-  return prec_upload("cf_prec_create_inv", K, n, device, out);
-}
-
-extern "C" void cf_prec_destroy(cf_prec* p) {
-  if (!p) return;
-  DeviceScope on_device(p->device);
-  delete p;
-}
-
-extern "C" int cf_prec_diag(cf_prec* p, double* out_n) {
-  if (!p || !out_n) return fail(CF_ERR_INVALID, "cf_prec_diag: null argument");
-  memcpy(out_n, p->kdiag_host.data(), p->kdiag_host.size() * 8);
-  return CF_OK;
-}
-
-// what cosmofit_group.hip reads of a cf_prec (cosmofit_group.h)
-int cf_prec_look(const cf_prec* p, cf_prec_view* out) {
-  if (!p || !out) return fail(CF_ERR_INVALID, "cf_group: null cf_prec");
-  *out = cf_prec_view{p->n, p->kp, p->device, p->K.as<const double>(), p->kdiag_host.data()};
-  return CF_OK;
-}
-
-extern "C" int cf_prec_apply_device(cf_prec* p, const double* d_rows, int64_t pitch, int64_t S, double* d_g, int64_t g_pitch,
-                                    void* hip_stream) {
-  const std::string F = "cf_prec_apply_device: ";
-  if (!p) return fail(CF_ERR_INVALID, F + "null cf_prec");
-  if (S < 0 || S > CF_RESID_MAX_ROWS) return fail(CF_ERR_INVALID, F + "S out of range");
-  if (pitch < p->n || g_pitch < p->n) return fail(CF_ERR_INVALID, F + "a pitch below n");
-  if (S == 0) return CF_OK;
-  if (!d_rows || !d_g) return fail(CF_ERR_INVALID, F + "null rows or g");
-  DeviceScope on_device(p->device);
-  HIP_TRY(on_device.err);
-  const cf_infl_src src{d_rows, nullptr, pitch, (int32_t)p->n, 0};
-  return cf_prec_gemm_launch(src, S, p->K.as<const double>(), p->kp, d_g, g_pitch, (hipStream_t)hip_stream);
-}
-
-static int infl_check_acc(const std::string& F, const char* name, const cf_resid_acc* acc, int64_t n, int32_t n_thr) {
-  const std::string A = F + name;
-  if (acc->struct_size != (int32_t)sizeof(cf_resid_acc)) return fail(CF_ERR_INVALID, A + ".struct_size mismatch");
-  if (acc->n != n) return fail(CF_ERR_INVALID, A + ".n is not the number of data of the block");
-  if (acc->n_thr != n_thr) return fail(CF_ERR_INVALID, A + (n_thr ? ".n_thr differs from n_thr" : ".n_thr must be 0"));
-  if (acc_lacks_an_array(acc, n_thr)) return fail(CF_ERR_INVALID, A + " has a null array");
-  return CF_OK;
-}
-
-extern "C" int cf_infl_check_args(int64_t n_sn, int32_t n_bao, int32_t is_quasar, int32_t n_devices, int32_t handle_device,
-                                  int32_t has_prec, int64_t prec_n, int32_t prec_device, const void* theta, int64_t S, int32_t block,
-                                  const double* thresholds, int32_t n_thr, const cf_infl_out* out, const cf_resid_acc* acc_z,
-                                  const cf_resid_acc* acc_contrib) {
-  const std::string F = "cf_infl: ";
-  if (is_quasar) return fail(CF_ERR_INVALID, F + "a quasar handle has no accessor path to take the residuals from");
-  if (n_devices > 1) return fail(CF_ERR_INVALID, F + "this handle spans several devices; use one handle per device");
-  int rc;
-  if ((rc = check_block(F, n_sn, n_bao, block))) return rc;
-  const int64_t n = block == CF_RB_SN ? n_sn : n_bao;
-  if (!has_prec) return fail(CF_ERR_INVALID, F + "null cf_prec");
-  if (prec_n != n) return fail(CF_ERR_INVALID, F + "cf_prec.n is not the number of data of the block");
-  if (prec_device != handle_device) return fail(CF_ERR_INVALID, F + "the cf_prec lives on another device than the handle");
-  if ((rc = check_rows_thresholds(F, S, thresholds, n_thr))) return rc;
-  if (out && out->struct_size != (int32_t)sizeof(cf_infl_out)) return fail(CF_ERR_INVALID, F + "cf_infl_out.struct_size mismatch");
-  const bool any_out = out && (out->g || out->contrib || out->z || out->loo || out->sample);
-  if (!any_out && !acc_z && !acc_contrib) return fail(CF_ERR_INVALID, F + "no output requested");
-  if (acc_z && (rc = infl_check_acc(F, "acc_z", acc_z, n, n_thr))) return rc;
-  if (acc_contrib && (rc = infl_check_acc(F, "acc_contrib", acc_contrib, n, 0))) return rc;
-  if (S > 0 && !theta) return fail(CF_ERR_INVALID, F + "null theta");
-  return CF_OK;
-}
-
-static int infl_check(cf_handle* h, cf_prec* prec, const void* theta, int64_t S, int32_t block, const double* thresholds,
-                      int32_t n_thr, const cf_infl_out* out, const cf_resid_acc* acc_z, const cf_resid_acc* acc_contrib) {
-  if (!h) return fail(CF_ERR_INVALID, "cf_infl: null handle");
-  return cf_infl_check_args(h->d.n_sn, h->d.n_bao, h->qsr ? 1 : 0, 1 + (int32_t)h->peers.size(), h->device, prec ? 1 : 0,
-                            prec ? prec->n : 0, prec ? prec->device : 0, theta, S, block, thresholds, n_thr, out, acc_z, acc_contrib);
-}
-
-extern "C" int cf_infl_set_chunk(cf_handle* h, int64_t rows) { return set_chunk(h, &cf_handle::infl_chunk, rows, "cf_infl_set_chunk"); }
-
-// The chunk buffers of g and of the contrib / z rows.  Growing frees buffers an earlier call on a caller's stream may still use:
-// synchronise first, as resid_prepare does.
-static int infl_prepare(const HandleScope& hs, int64_t rows, int64_t n, bool need_g, bool need_contrib, bool need_z) {
-  cf_handle* const h = hs.h;
-  const size_t bytes = (size_t)rows * (size_t)n * 8;
-  DevBuf* const buf[3] = {&h->i_g, &h->i_contrib, &h->i_z};
-  const bool need[3] = {need_g, need_contrib, need_z};
-  bool grow = false;
-  for (int k = 0; k < 3; ++k) grow = grow || (need[k] && bytes > buf[k]->bytes);
-  if (!grow) return 0;
-  HIP_TRY(hipDeviceSynchronize());
-  for (int k = 0; k < 3; ++k)
-    if (need[k] && buf[k]->ensure(bytes)) return CF_ERR_HIP;
-  return 0;
-}
-
-// Arguments checked.  Device pointers throughout.
-static int infl_run(const HandleScope& hs, const cf_prec* prec, const double* d_theta, int64_t S, const double* d_w, int32_t block,
-                    const double* thresholds, int32_t n_thr, const cf_infl_out& out, const cf_resid_acc* acc_z,
-                    const cf_resid_acc* acc_contrib, hipStream_t st) {
-  cf_handle* const h = hs.h;
-  int rc;
-  const int64_t chunk = std::min<int64_t>(S, h->infl_chunk > 0 ? h->infl_chunk : CF_INFL_CHUNK);
-  if ((rc = ensure_workspace(h, chunk))) return rc;
-  if ((rc = resid_prepare(hs, chunk))) return rc;
-  const int64_t n = prec->n;
-  if ((rc = infl_prepare(hs, chunk, n, !out.g, acc_contrib && !out.contrib, acc_z && !out.z))) return rc;
-  const cf_dev_desc& d = h->d;
-  const cf_infl_src src = block == CF_RB_SN
-                              ? cf_infl_src{h->delta.as<const double>(), nullptr, (int64_t)d.n_ld, (int32_t)d.n_sn, 0}
-                              : cf_infl_src{h->r_bt.as<const double>(), d.bao_val, (int64_t)d.n_bao, (int32_t)d.n_bao, 1};
-  const cf_resid_blocks no_blocks{nullptr, nullptr, nullptr, nullptr};
-  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-    const int64_t m = std::min(chunk, S - s0);
-    // a mu_corr buffer selects the accessor form of the per-walker kernel (residual rows in row layout), as in resid_run
-    if ((rc = launch_path(h, d_theta + s0 * d.ndim, m, h->out.as<double>(), CF_OUT_CHI2, st, nullptr,
-                          d.n_sn > 0 ? h->r_mc.as<double>() : nullptr, nullptr, d.n_bao > 0 ? h->r_bt.as<double>() : nullptr)))
-      return rc;
-    double* g = out.g ? out.g + s0 * n : h->i_g.as<double>();
-    if ((rc = cf_prec_gemm_launch(src, m, prec->K.as<const double>(), prec->kp, g, n, st))) return rc;
-    cf_infl_rows a{};
-    a.g = g;
-    a.g_pitch = n;
-    a.kdiag = prec->kdiag.as<const double>();
-    a.inv_sqrt_kdiag = prec->inv_sqrt_kdiag.as<const double>();
-    a.contrib = out.contrib ? out.contrib + s0 * n : (acc_contrib ? h->i_contrib.as<double>() : nullptr);
-    a.z = out.z ? out.z + s0 * n : (acc_z ? h->i_z.as<double>() : nullptr);
-    a.loo = out.loo ? out.loo + s0 * n : nullptr;
-    a.sample = out.sample ? out.sample + (int64_t)CF_INFL_NCOL * s0 : nullptr;
-    if (a.contrib || a.z || a.loo || a.sample)
-      if ((rc = cf_infl_row_launch(src, m, a, st))) return rc;
-    cf_resid_src rows{};
-    rows.sigma = prec->ones.as<const double>();
-    rows.pitch = n;
-    rows.n = (int32_t)n;
-    if (acc_z) {
-      rows.rows = a.z;
-      if ((rc = cf_resid_launch(rows, m, nullptr, no_blocks, d_w ? d_w + s0 : nullptr, thresholds, n_thr, acc_z, st))) return rc;
-    }
-    if (acc_contrib) {
-      rows.rows = a.contrib;
-      if ((rc = cf_resid_launch(rows, m, nullptr, no_blocks, d_w ? d_w + s0 : nullptr, nullptr, 0, acc_contrib, st))) return rc;
-    }
-  }
-  return CF_OK;
-}
-
-extern "C" int cf_infl_device(cf_handle* h, cf_prec* prec, const double* d_theta, int64_t S, const double* d_w, int32_t block,
-                              const double* thresholds, int32_t n_thr, cf_infl_out* out, cf_resid_acc* acc_z,
-                              cf_resid_acc* acc_contrib, void* hip_stream) {
-  int rc = infl_check(h, prec, d_theta, S, block, thresholds, n_thr, out, acc_z, acc_contrib);
-  if (rc) return rc;
-  if (S == 0) return CF_OK;
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  return infl_run(hs, prec, d_theta, S, d_w, block, thresholds, n_thr, out ? *out : cf_infl_out{}, acc_z, acc_contrib,
-                  (hipStream_t)hip_stream);
-}
-
-// Host-buffer twin: rows in pieces through temporary device buffers on the handle's own stream (a piece is a chunk: the row
-// arrays are [piece][n]).
-#define CF_INFL_HOST_PIECE 4096
-
-extern "C" int cf_infl(cf_handle* h, cf_prec* prec, const double* theta, int64_t S, const double* w, int32_t block,
-                       const double* thresholds, int32_t n_thr, cf_infl_out* out, cf_resid_acc* acc_z, cf_resid_acc* acc_contrib) {
-  int rc = infl_check(h, prec, theta, S, block, thresholds, n_thr, out, acc_z, acc_contrib);
-  if (rc) return rc;
-  if (S == 0) return CF_OK;
-  HandleScope hs(h);
-  HIP_TRY(hs.err);
-  const size_t row = (size_t)prec->n * 8;
-  const cf_infl_out ho = out ? *out : cf_infl_out{};
-  RowStage rows(h->stream, std::min<int64_t>(S, CF_INFL_HOST_PIECE));
-  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
-  const double* dw = rows.in(w, 8);
-  cf_infl_out dout{};
-  dout.struct_size = (int32_t)sizeof(cf_infl_out);
-  dout.g = rows.out(ho.g, row); dout.contrib = rows.out(ho.contrib, row); dout.z = rows.out(ho.z, row); dout.loo = rows.out(ho.loo, row);
-  dout.sample = rows.out(ho.sample, (size_t)CF_INFL_NCOL * 8);
-  HostAccTwin az, ac;
-  if ((rc = az.up(acc_z, h->stream)) || (rc = ac.up(acc_contrib, h->stream))) return rc;
-  if ((rc = rows.run(S, [&](int64_t, int64_t m) {
-         return infl_run(hs, prec, dth, m, dw, block, thresholds, n_thr, dout, az.ptr(), ac.ptr(), h->stream);
-       })))
-    return rc;
-  if ((rc = az.down()) || (rc = ac.down())) return rc;
   return CF_OK;
 }

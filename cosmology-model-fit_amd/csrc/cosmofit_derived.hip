@@ -30,10 +30,11 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <cmath>
 #include <string>
 
 #include "../../include/cosmofit.h"
-#include "cf_host.h"
+#include "cf_handle.h"
 #include "cosmofit_device.h"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -378,16 +379,16 @@ curves_kernel(cf_dev_desc d, const double* __restrict__ theta, int64_t S, int co
 }
 
 // ------------------------------------------------------------------------------------------------
-// Launchers (arguments are validated by cosmofit_api.hip)
+// Launchers (arguments are validated by the entry points below)
 // ------------------------------------------------------------------------------------------------
-int cf_derived_launch(const cf_dev_desc& d, const cf_derived_kargs& a, const double* d_theta, int64_t S, double* d_out,
+static int cf_derived_launch(const cf_dev_desc& d, const cf_derived_kargs& a, const double* d_theta, int64_t S, double* d_out,
                       hipStream_t st) {
   const int64_t blocks = (S + DQ_TPB - 1) / DQ_TPB;
   hipLaunchKernelGGL(derived_kernel, dim3((unsigned)blocks), dim3(DQ_TPB), 0, st, d, a, d_theta, S, d_out);
   return cf_launch_status("cf_derived_device");
 }
 
-int cf_curves_launch(const cf_dev_desc& d, const double* d_theta, int64_t S, int code, const double* d_z, int nz, double* d_out,
+static int cf_curves_launch(const cf_dev_desc& d, const double* d_theta, int64_t S, int code, const double* d_z, int nz, double* d_out,
                      hipStream_t st) {
   const int chs = dq_chunk_shift(d.n_grid);
   const size_t lds = dq_table_slots(d.n_grid, chs) * sizeof(d2) + (DQ_TPB + 2) * sizeof(double);
@@ -407,4 +408,225 @@ int cf_curves_launch(const cf_dev_desc& d, const double* d_theta, int64_t S, int
   }
   hipLaunchKernelGGL(curves_kernel, dim3((unsigned)S), dim3(DQ_TPB), lds, st, d, d_theta, S, code, chs, d_z, nz, d_out);
   return cf_launch_status("cf_curves_device");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Entry points: what each quantity and curve needs of the handle, the device paths and their host-buffer twins
+// ------------------------------------------------------------------------------------------------
+
+static const char* dq_name(int code) {
+  switch (code) {
+    case CF_DQ_H0: return "H0";
+    case CF_DQ_H: return "h";
+    case CF_DQ_OM: return "Om";
+    case CF_DQ_OMH2: return "omh2";
+    case CF_DQ_OBH2: return "obh2";
+    case CF_DQ_OCH2: return "och2";
+    case CF_DQ_W0: return "w0";
+    case CF_DQ_WA: return "wa";
+    case CF_DQ_Q0: return "q0";
+    case CF_DQ_J0: return "j0";
+    case CF_DQ_S8: return "S8";
+    case CF_DQ_RD: return "rd";
+    case CF_DQ_Z_STAR: return "z_star";
+    case CF_DQ_R_DRAG: return "r_drag";
+    case CF_DQ_Z_DRAG: return "z_drag";
+    case CF_DQ_Z_EQ: return "z_eq";
+    case CF_DQ_H_AT: return "H@z";
+    case CF_DQ_RS_STAR: return "rs_star";
+    case CF_DQ_DM_STAR: return "DM_star";
+    case CF_DQ_THETA_STAR100: return "theta_star100";
+    case CF_DQ_R: return "R";
+    case CF_DQ_LA: return "lA";
+    default: return nullptr;
+  }
+}
+static const char* curve_name(int code) {
+  static const char* names[] = {"H", "DM", "DV_rd", "DM_rd", "DH_rd", "F_AP", "mu"};
+  return code >= CF_CURVE_H && code <= CF_CURVE_MU ? names[code] : nullptr;
+}
+
+// a slot the descriptor filled: a theta index, or a non-zero constant (an unused slot is {idx -1, fixed 0})
+static bool slot_present(const cf_dev_desc& d, int s) { return d.slot[s].idx >= 0 || d.slot[s].fixed != 0.0; }
+
+// What a quantity reads of the handle; the first thing that is missing, or nullptr.
+static const char* missing_h0(const cf_dev_desc& d) { return slot_present(d, CF_P_H0) ? nullptr : "an H0 slot"; }
+static const char* missing_wb_wc(const cf_dev_desc& d) {
+  if (!slot_present(d, CF_P_OBH2)) return "an obh2 slot";
+  if (!slot_present(d, CF_P_OCH2)) return "an och2 slot";
+  return nullptr;
+}
+static const char* missing_om(const cf_dev_desc& d) {
+  if (d.ez_model == CF_EZ_PHYSICAL) {
+    if (const char* m = missing_h0(d)) return m;
+    return missing_wb_wc(d);
+  }
+  if (!slot_present(d, CF_P_OM)) return "an Om slot";
+  return d.om_mode ? missing_h0(d) : nullptr;
+}
+static const char* missing_wm_drag(const cf_dev_desc& d) {  // wb and the matter density of the r_drag / z_drag fits
+  if (!slot_present(d, CF_P_OBH2)) return "an obh2 slot";
+  if (d.rd_wm_late) {
+    if (const char* m = missing_h0(d)) return m;
+    return slot_present(d, CF_P_OM) ? nullptr : "an Om slot";
+  }
+  return slot_present(d, CF_P_OCH2) ? nullptr : "an och2 slot";
+}
+static const char* missing_rd(const cf_dev_desc& d) {
+  if (d.rd_from_fit) return missing_wm_drag(d);
+  return slot_present(d, CF_P_RD) ? nullptr : "an r_d slot or the r_drag fit (CF_RD_FIT)";
+}
+
+static int derived_prepare(cf_handle* h, const int32_t* codes, const double* args, int32_t n_q, const cf_derived_consts* consts,
+                           cf_derived_kargs& a, const char* fn) {
+  const std::string F = std::string(fn) + ": ";
+  if (h->qsr) return cf_set_error(CF_ERR_UNSUPPORTED, F + "a quasar handle has no derived quantities");
+  if (!h->peers.empty()) return cf_set_error(CF_ERR_INVALID, F + "this handle spans several devices; use one handle per device");
+  if (!codes) return cf_set_error(CF_ERR_INVALID, F + "null argument");
+  if (n_q < 1 || n_q > CF_DQ_MAX) return cf_set_error(CF_ERR_INVALID, F + "n_q must be in 1.." + std::to_string(CF_DQ_MAX));
+  if (consts && consts->struct_size != (int32_t)sizeof(cf_derived_consts)) return cf_set_error(CF_ERR_INVALID, F + "cf_derived_consts.struct_size mismatch");
+  const cf_dev_desc& d = h->d;
+  memset(&a, 0, sizeof(a));
+  a.n_q = n_q;
+  for (int q = 0; q < n_q; ++q) {
+    const int code = codes[q];
+    const char* name = dq_name(code);
+    if (!name) return cf_set_error(CF_ERR_INVALID, F + "unknown quantity code " + std::to_string(code));
+    const char* miss = nullptr;
+    double arg = args ? args[q] : 0.0;
+    switch (code) {
+      case CF_DQ_H0: case CF_DQ_H: miss = missing_h0(d); break;
+      case CF_DQ_OM: case CF_DQ_Q0: case CF_DQ_J0: miss = missing_om(d); break;
+      case CF_DQ_OMH2:
+        miss = d.ez_model == CF_EZ_PHYSICAL ? missing_wb_wc(d) : (missing_h0(d) ? missing_h0(d) : missing_om(d));
+        break;
+      case CF_DQ_OBH2: miss = slot_present(d, CF_P_OBH2) ? nullptr : "an obh2 slot"; break;
+      case CF_DQ_OCH2: miss = slot_present(d, CF_P_OCH2) ? nullptr : "an och2 slot"; break;
+      case CF_DQ_W0: case CF_DQ_WA: break;
+      case CF_DQ_S8: miss = slot_present(d, CF_P_S8) ? missing_om(d) : "a sigma8 slot"; break;
+      case CF_DQ_RD:
+        miss = missing_rd(d);
+        if (d.rd_from_fit) a.need |= CF_DQ_NEED_RDFIT;
+        break;
+      case CF_DQ_Z_STAR:
+        miss = d.cmb_mode == CF_CMB_NONE ? "a compressed-CMB block (z_star coefficients)" : missing_wb_wc(d);
+        a.need |= CF_DQ_NEED_ZSTAR;
+        break;
+      case CF_DQ_R_DRAG:
+        miss = (d.rd_from_fit || (consts && consts->has_rdrag_fit)) ? missing_wm_drag(d) : "r_drag coefficients (CF_RD_FIT or cf_derived_consts.rdrag_fit)";
+        a.need |= CF_DQ_NEED_RDFIT;
+        break;
+      case CF_DQ_Z_DRAG:
+        miss = consts ? missing_wm_drag(d) : "cf_derived_consts.zdrag_fit";
+        a.need |= CF_DQ_NEED_ZDRAG;
+        break;
+      case CF_DQ_Z_EQ:
+        miss = missing_wb_wc(d);
+        if (!(arg > 0.0)) arg = consts ? consts->zeq_or_h2 : 0.0;
+        if (!miss && !(arg > 0.0 && std::isfinite(arg))) miss = "Omega_r h^2 > 0 (arg or cf_derived_consts.zeq_or_h2)";
+        break;
+      case CF_DQ_H_AT:
+        miss = missing_h0(d) ? missing_h0(d) : (std::isfinite(arg) ? nullptr : "a finite redshift");
+        break;
+      default:  // the Gauss-Legendre quantities
+        miss = (d.n_gl < 1 || !d.gl_x || !d.gl_w) ? "Gauss-Legendre nodes (a compressed-CMB block)"
+                                                  : (missing_h0(d) ? missing_h0(d) : missing_wb_wc(d));
+        a.need |= CF_DQ_NEED_GL | CF_DQ_NEED_ZSTAR;
+        break;
+    }
+    if (miss) return cf_set_error(CF_ERR_INVALID, F + name + " needs " + miss + ", which this handle lacks");
+    a.codes[q] = code;
+    a.args[q] = arg;
+  }
+  if (consts)
+    for (int i = 0; i < 10; ++i) a.zdrag_fit[i] = consts->zdrag_fit[i];
+  for (int i = 0; i < 11; ++i) a.rdrag_fit[i] = d.rd_from_fit ? d.rd_fit[i] : (consts && consts->has_rdrag_fit ? consts->rdrag_fit[i] : 0.0);
+  return CF_OK;
+}
+
+static int curves_check(cf_handle* h, int32_t code, int32_t nz, const char* fn) {
+  const std::string F = std::string(fn) + ": ";
+  if (h->qsr) return cf_set_error(CF_ERR_UNSUPPORTED, F + "a quasar handle has no prediction curves; use cf_qsr_eval_parts");
+  if (!h->peers.empty()) return cf_set_error(CF_ERR_INVALID, F + "this handle spans several devices; use one handle per device");
+  const char* name = curve_name(code);
+  if (!name) return cf_set_error(CF_ERR_INVALID, F + "unknown curve code " + std::to_string(code));
+  if (nz < 1 || nz > CF_CURVE_MAX_NZ) return cf_set_error(CF_ERR_INVALID, F + "nz must be in 1.." + std::to_string(CF_CURVE_MAX_NZ));
+  const cf_dev_desc& d = h->d;
+  const char* miss = missing_h0(d);
+  if (!miss && d.ez_model == CF_EZ_PHYSICAL) miss = missing_wb_wc(d);
+  if (!miss && d.ez_model != CF_EZ_PHYSICAL) miss = missing_om(d);
+  if (!miss && (code == CF_CURVE_DV_RD || code == CF_CURVE_DM_RD || code == CF_CURVE_DH_RD)) miss = missing_rd(d);
+  if (!miss && !d.bao_dh_exact && d.n_grid < 3 && (code == CF_CURVE_DV_RD || code == CF_CURVE_DH_RD || code == CF_CURVE_FAP))
+    miss = "n_grid >= 3 (PCHIP D_H)";
+  if (miss) return cf_set_error(CF_ERR_INVALID, F + name + " needs " + miss + ", which this handle lacks");
+  return CF_OK;
+}
+
+#define CF_DQ_MAX_ROWS (((int64_t)1 << 31) - 1)
+
+extern "C" int cf_derived_device(cf_handle* h, const double* d_theta, int64_t S, const int32_t* codes, const double* args, int32_t n_q,
+                                 const cf_derived_consts* consts, double* d_out, void* hip_stream) {
+  if (!h) return cf_set_error(CF_ERR_INVALID, "cf_derived_device: null argument");
+  cf_derived_kargs a;
+  int rc = derived_prepare(h, codes, args, n_q, consts, a, "cf_derived_device");
+  if (rc) return rc;
+  if (S < 0 || S > CF_DQ_MAX_ROWS) return cf_set_error(CF_ERR_INVALID, "cf_derived_device: S out of range");
+  if (S == 0) return CF_OK;
+  if (!d_theta || !d_out) return cf_set_error(CF_ERR_INVALID, "cf_derived_device: null argument");
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  return cf_derived_launch(h->d, a, d_theta, S, d_out, (hipStream_t)hip_stream);
+}
+
+extern "C" int cf_curves_device(cf_handle* h, const double* d_theta, int64_t S, int32_t code, const double* d_z, int32_t nz,
+                                double* d_out, void* hip_stream) {
+  if (!h) return cf_set_error(CF_ERR_INVALID, "cf_curves_device: null argument");
+  int rc = curves_check(h, code, nz, "cf_curves_device");
+  if (rc) return rc;
+  if (S < 0 || S > CF_DQ_MAX_ROWS) return cf_set_error(CF_ERR_INVALID, "cf_curves_device: S out of range");
+  if (S == 0) return CF_OK;
+  if (!d_theta || !d_z || !d_out) return cf_set_error(CF_ERR_INVALID, "cf_curves_device: null argument");
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  return cf_curves_launch(h->d, d_theta, S, code, d_z, nz, d_out, (hipStream_t)hip_stream);
+}
+
+// Host-buffer twins: rows in chunks through temporary device buffers on the handle's own stream.
+#define CF_DQ_HOST_CHUNK 65536
+
+extern "C" int cf_derived(cf_handle* h, const double* theta, int64_t S, const int32_t* codes, const double* args, int32_t n_q,
+                          const cf_derived_consts* consts, double* out) {
+  if (!h) return cf_set_error(CF_ERR_INVALID, "cf_derived: null argument");
+  cf_derived_kargs a;
+  int rc = derived_prepare(h, codes, args, n_q, consts, a, "cf_derived");
+  if (rc) return rc;
+  if (S < 0 || S > CF_DQ_MAX_ROWS) return cf_set_error(CF_ERR_INVALID, "cf_derived: S out of range");
+  if (S == 0) return CF_OK;
+  if (!theta || !out) return cf_set_error(CF_ERR_INVALID, "cf_derived: null argument");
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  RowStage rows(h->stream, std::min<int64_t>(S, CF_DQ_HOST_CHUNK));
+  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
+  double* dout = rows.out(out, (size_t)n_q * 8);
+  return rows.run(S, [&](int64_t, int64_t m) { return cf_derived_launch(h->d, a, dth, m, dout, h->stream); });
+}
+
+extern "C" int cf_curves(cf_handle* h, const double* theta, int64_t S, int32_t code, const double* z, int32_t nz, double* out) {
+  if (!h) return cf_set_error(CF_ERR_INVALID, "cf_curves: null argument");
+  int rc = curves_check(h, code, nz, "cf_curves");
+  if (rc) return rc;
+  if (S < 0 || S > CF_DQ_MAX_ROWS) return cf_set_error(CF_ERR_INVALID, "cf_curves: S out of range");
+  if (S == 0) return CF_OK;
+  if (!theta || !z || !out) return cf_set_error(CF_ERR_INVALID, "cf_curves: null argument");
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  RowStage rows(h->stream, std::min<int64_t>(S, std::max<int64_t>(1, CF_DQ_HOST_CHUNK * 16 / nz)));
+  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
+  double* dout = rows.out(out, (size_t)nz * 8);
+  DevBuf dz;
+  if (dz.ensure((size_t)nz * 8)) return CF_ERR_HIP;
+  HIP_TRY(hipMemcpyAsync(dz.p, z, (size_t)nz * 8, hipMemcpyHostToDevice, h->stream));
+  return rows.run(S, [&](int64_t, int64_t m) {
+    return cf_curves_launch(h->d, dth, m, code, dz.as<const double>(), nz, dout, h->stream);
+  });
 }

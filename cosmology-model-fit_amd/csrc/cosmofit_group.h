@@ -1,4 +1,4 @@
-// cosmofit_group.h -- what cosmofit_api.hip (the owner of cf_prec) and cosmofit_group.hip (the group object, its kernels and the
+// cosmofit_group.h -- what cosmofit_infl.hip (the owner of cf_prec) and cosmofit_group.hip (the group object, its kernels and the
 // importance summary) share.
 #ifndef COSMOFIT_GROUP_H
 #define COSMOFIT_GROUP_H
@@ -14,6 +14,6 @@ struct cf_prec_view {
   const double* d_K;
   const double* kdiag_host;
 };
-int cf_prec_look(const cf_prec* p, cf_prec_view* out);  // cosmofit_api.hip; CF_ERR_INVALID for a null cf_prec
+int cf_prec_look(const cf_prec* p, cf_prec_view* out);  // cosmofit_infl.hip; CF_ERR_INVALID for a null cf_prec
 
 #endif

@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(GQ_TPB) group_quad_kernel(cf_group_dev gd, con
 // ------------------------------------------------------------------------------------------------
 #define CF_GROUP_MAX_N 32768
 
-// s + c carries the running sum (Knuth's TwoSum, branch-free), as prec_add of cosmofit_api.hip
+// s + c carries the running sum (Knuth's TwoSum, branch-free), as prec_add of cosmofit_infl.hip
 static inline void grp_add(long double& s, long double& c, long double p) {
   const long double t = s + p, z = t - s;
   c += (s - (t - z)) + (p - z);

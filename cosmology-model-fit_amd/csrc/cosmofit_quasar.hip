@@ -32,7 +32,7 @@
 #include <vector>
 
 #include "../../include/cosmofit.h"
-#include "cf_host.h"
+#include "cf_handle.h"
 #include "cf_wave_scan.h"
 #include "cosmofit_device.h"
 
@@ -188,7 +188,7 @@ struct cf_qsr_state {
   std::vector<void*> bufs;
   int64_t n_qsr = 0;
   int32_t n_bao = 0;
-  // accessor outputs (device), set around one launch under the handle's lock by cf_qsr_eval_parts
+  // accessor outputs (device), set around one launch under the handle's lock by cf_qsr_eval_parts (below)
   double* parts = nullptr;
   double* mu_sn = nullptr;
   double* mu_q = nullptr;
@@ -259,7 +259,7 @@ static cf_dev_slot qsr_dev_slot(const cf_param& p) {
 }
 
 // Validate the extension against the descriptor and upload every table on the current device.
-int cf_qsr_prepare(const cf_desc* c, const cf_qsr_ext* e, int64_t n_ld, cf_qsr_state** out) {
+static int cf_qsr_prepare(const cf_desc* c, const cf_qsr_ext* e, int64_t n_ld, cf_qsr_state** out) {
   *out = nullptr;
   auto bad = [](const char* m) { return cf_set_error(CF_ERR_INVALID, std::string("cf_create_quasar: ") + m); };
   if (e->struct_size != (int32_t)sizeof(cf_qsr_ext)) return bad("extension size mismatch");
@@ -371,12 +371,6 @@ int cf_qsr_prepare(const cf_desc* c, const cf_qsr_ext* e, int64_t n_ld, cf_qsr_s
   return 0;
 }
 
-int64_t cf_qsr_n_qsr(const cf_qsr_state* q) { return q->n_qsr; }
-int32_t cf_qsr_n_bao(const cf_qsr_state* q) { return q->n_bao; }
-void cf_qsr_set_outputs(cf_qsr_state* q, double* parts, double* mu_sn, double* mu_q, double* bao) {
-  q->parts = parts, q->mu_sn = mu_sn, q->mu_q = mu_q, q->bao = bao;
-}
-
 // The per-walker kernel of one evaluation on `st`: SN residuals into delta, chi2_q (+ sum ln) + chi2_bao into extra.
 int cf_qsr_launch(const cf_qsr_state* q, const double* theta, int64_t W, double* delta, double* extra, int out_kind,
                   double* th_copy, hipStream_t st) {
@@ -402,4 +396,74 @@ int cf_qsr_launch(const cf_qsr_state* q, const double* theta, int64_t W, double*
                      out_kind != CF_OUT_CHI2 ? 1 : 0, th_copy, q->parts, q->mu_sn, q->mu_q, q->bao);
   // a refused launch is this call's error: the kernels behind it would otherwise finish the evaluation on stale residuals
   return cf_launch_status("cf_qsr_launch: qsr_walker_kernel (or an earlier HIP call of this thread)");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Entry points.  A quasar handle is an ordinary handle (cf_handle.h) whose per-walker kernel is the one above; the SN solve, the
+// epilogue, the workspace, timing and the completion words are the handle's own.
+// ------------------------------------------------------------------------------------------------
+extern "C" int cf_create_quasar(const cf_desc* c, const cf_qsr_ext* e, cf_handle** out) {
+  if (!c || !e || !out) return cf_set_error(CF_ERR_INVALID, "cf_create_quasar: null argument");
+  *out = nullptr;
+  if (c->n_devices != 0) return cf_set_error(CF_ERR_UNSUPPORTED, "cf_create_quasar: a quasar handle lives on one device (n_devices must be 0)");
+  int rc = validate_desc(c);
+  if (rc) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return cf_set_error(CF_ERR_NO_DEVICE, "cf_create_quasar: no HIP device visible (this library has no CPU path)");
+  if (c->device < 0 || c->device >= ndev) return cf_set_error(CF_ERR_INVALID, "cf_create_quasar: device ordinal out of range");
+  HostPrep prep;
+  cf_handle* h = nullptr;
+  if ((rc = create_one(c, c->device, prep, &h))) return rc;
+  {
+    DeviceScope on_device(h->device);
+    if (on_device.err != hipSuccess) rc = cf_set_error(CF_ERR_HIP, "hipSetDevice failed");
+    else rc = cf_qsr_prepare(c, e, h->d.n_ld, &h->qsr);
+  }
+  if (rc) {
+    const std::string keep = cf_last_error();
+    cf_destroy(h);
+    return cf_set_error(rc, keep);
+  }
+  *out = h;
+  return CF_OK;
+}
+
+extern "C" int cf_qsr_eval_parts(cf_handle* h, const double* theta, int64_t W, double* chi2_blocks, double* mu_sn, double* mu_qsr,
+                                 double* bao_theory) {
+  if (!h || !theta) return cf_set_error(CF_ERR_INVALID, "cf_qsr_eval_parts: null argument");
+  if (!h->qsr) return cf_set_error(CF_ERR_INVALID, "cf_qsr_eval_parts: not a quasar handle (cf_create_quasar)");
+  if (W <= 0 || W > (1 << 20)) return cf_set_error(CF_ERR_INVALID, "cf_qsr_eval_parts: W out of range");
+  if (mu_sn && h->d.n_sn == 0) return cf_set_error(CF_ERR_INVALID, "cf_qsr_eval_parts: this likelihood has no SN block");
+  cf_qsr_state* const q = h->qsr;
+  const int64_t nq = q->n_qsr, nb = q->n_bao, n = h->d.n_sn;
+  if (bao_theory && nb == 0) return cf_set_error(CF_ERR_INVALID, "cf_qsr_eval_parts: this likelihood has no BAO block");
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  int rc;
+  if ((rc = ensure_workspace(h, W))) return rc;
+  DevBuf parts, snb, ms, mq, bt;
+  if (parts.ensure((size_t)W * 3 * 8) || snb.ensure((size_t)W * 8)) return CF_ERR_HIP;
+  HIP_TRY(hipMemsetAsync(parts.p, 0, (size_t)W * 3 * 8, h->stream));
+  HIP_TRY(hipMemsetAsync(snb.p, 0, (size_t)W * 8, h->stream));
+  if (mu_sn && ms.ensure((size_t)W * n * 8)) return CF_ERR_HIP;
+  if (mu_qsr && mq.ensure((size_t)W * nq * 8)) return CF_ERR_HIP;
+  if (bao_theory && bt.ensure((size_t)W * nb * 8)) return CF_ERR_HIP;
+  HIP_TRY(hipMemcpyAsync(h->theta.p, theta, (size_t)W * h->d.ndim * 8, hipMemcpyHostToDevice, h->stream));
+  q->parts = parts.as<double>(), q->mu_sn = ms.as<double>(), q->mu_q = mq.as<double>(), q->bao = bt.as<double>();
+  rc = launch_path(h, h->theta.as<const double>(), W, h->out.as<double>(), CF_OUT_CHI2, h->stream, nullptr, nullptr, nullptr, nullptr,
+                   n > 0 ? snb.as<double>() : nullptr);
+  q->parts = q->mu_sn = q->mu_q = q->bao = nullptr;
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (mu_sn) HIP_TRY(hipMemcpy(mu_sn, ms.p, (size_t)W * n * 8, hipMemcpyDeviceToHost));
+  if (mu_qsr) HIP_TRY(hipMemcpy(mu_qsr, mq.p, (size_t)W * nq * 8, hipMemcpyDeviceToHost));
+  if (bao_theory) HIP_TRY(hipMemcpy(bao_theory, bt.p, (size_t)W * nb * 8, hipMemcpyDeviceToHost));
+  if (chi2_blocks) {
+    std::vector<double> sn((size_t)W);
+    HIP_TRY(hipMemcpy(chi2_blocks, parts.p, (size_t)W * 3 * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sn.data(), snb.p, (size_t)W * 8, hipMemcpyDeviceToHost));
+    for (int64_t w = 0; w < W; ++w) chi2_blocks[3 * w] = sn[(size_t)w];
+  }
+  return CF_OK;
 }

@@ -1,5 +1,5 @@
 // cosmofit_resid.hip — the fit report of a chain: residual statistics of every sample and of every datum (include/cosmofit.h:
-// cf_resid_device; the launcher and the argument checks are in cosmofit_api.hip, the driver is
+// cf_resid_device; the kernels, then the argument checks and the chunk loop; the driver is
 // cosmology-model-fit_amd/fit_report.py).
 //
 // Every main() of the scripts ends by forming the data residuals at the central parameters and printing R^2, RMSD, skewness,
@@ -22,11 +22,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <string>
 
 #include "../../include/cosmofit.h"
-#include "cf_host.h"
-#include "cosmofit_device.h"
+#include "cf_handle.h"
 #include "cosmofit_resid.h"
 
 #define RS_TPB 256
@@ -175,4 +175,215 @@ int cf_resid_launch(const cf_resid_src& src, int64_t rows, double* d_sample, con
                        *acc);
   }
   return cf_launch_status("cf_resid_device");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host side.  The residual rows come from the accessor path of the likelihood (launch_path with a mu_corr buffer, as
+// cf_eval_parts), one chunk of rows at a time into the handle's workspace; the two kernels reduce each chunk behind it on the
+// same stream.
+// ------------------------------------------------------------------------------------------------
+// What cf_resid and cf_infl check alike (cosmofit_resid.h).  Their refusals of a quasar or multi-device handle differ in the
+// return code and their accumulator messages in the wording, so those stay with each.
+int check_block(const std::string& F, int64_t n_sn, int32_t n_bao, int32_t block) {
+  if (block != CF_RB_SN && block != CF_RB_BAO) return cf_set_error(CF_ERR_INVALID, F + "block must be CF_RB_SN or CF_RB_BAO");
+  if (block == CF_RB_SN && n_sn <= 0) return cf_set_error(CF_ERR_INVALID, F + "this likelihood has no SN block");
+  if (block == CF_RB_BAO && n_bao <= 0) return cf_set_error(CF_ERR_INVALID, F + "this likelihood has no BAO block");
+  return CF_OK;
+}
+int check_rows_thresholds(const std::string& F, int64_t S, const double* thresholds, int32_t n_thr) {
+  if (S < 0 || S > CF_RESID_MAX_ROWS) return cf_set_error(CF_ERR_INVALID, F + "S out of range");
+  if (n_thr < 0 || n_thr > CF_RESID_MAX_THR) return cf_set_error(CF_ERR_INVALID, F + "n_thr must be in 0..4");
+  if (n_thr > 0 && !thresholds) return cf_set_error(CF_ERR_INVALID, F + "null thresholds");
+  for (int k = 0; k < n_thr; ++k)
+    if (!std::isfinite(thresholds[k]) || thresholds[k] < 0.0) return cf_set_error(CF_ERR_INVALID, F + "thresholds must be finite and >= 0");
+  return CF_OK;
+}
+bool acc_lacks_an_array(const cf_resid_acc* acc, int32_t n_thr) {
+  return !acc->w_sum || !acc->mean || !acc->m2 || !acc->n_used || !acc->n_skipped || (n_thr > 0 && !acc->exceed);
+}
+
+extern "C" int cf_resid_check_args(int64_t n_sn, int32_t n_bao, int32_t is_quasar, int32_t n_devices, const void* theta, int64_t S,
+                                   int32_t block, const double* thresholds, int32_t n_thr, const void* sample, const void* chi2_blocks,
+                                   const cf_resid_acc* acc) {
+  const std::string F = "cf_resid: ";
+  int rc;
+  if (is_quasar) return cf_set_error(CF_ERR_UNSUPPORTED, F + "a quasar handle has no accessor path to take the residuals from");
+  if (n_devices > 1) return cf_set_error(CF_ERR_UNSUPPORTED, F + "this handle spans several devices; use one handle per device");
+  if ((rc = check_block(F, n_sn, n_bao, block))) return rc;
+  if ((rc = check_rows_thresholds(F, S, thresholds, n_thr))) return rc;
+  if (!sample && !chi2_blocks && !acc) return cf_set_error(CF_ERR_INVALID, F + "no output requested");
+  if (acc) {
+    const int64_t n = block == CF_RB_SN ? n_sn : n_bao;
+    if (acc->struct_size != (int32_t)sizeof(cf_resid_acc)) return cf_set_error(CF_ERR_INVALID, F + "cf_resid_acc.struct_size mismatch");
+    if (acc->n != n) return cf_set_error(CF_ERR_INVALID, F + "cf_resid_acc.n is not the number of data of the block");
+    if (acc->n_thr != n_thr) return cf_set_error(CF_ERR_INVALID, F + "cf_resid_acc.n_thr differs from n_thr");
+    if (acc_lacks_an_array(acc, n_thr)) return cf_set_error(CF_ERR_INVALID, F + "null array in cf_resid_acc");
+  }
+  if (S > 0 && !theta) return cf_set_error(CF_ERR_INVALID, F + "null theta");
+  return CF_OK;
+}
+
+static int resid_check(cf_handle* h, const void* theta, int64_t S, int32_t block, const double* thresholds, int32_t n_thr,
+                       const void* sample, const void* chi2_blocks, const cf_resid_acc* acc) {
+  if (!h) return cf_set_error(CF_ERR_INVALID, "cf_resid: null handle");
+  return cf_resid_check_args(h->d.n_sn, h->d.n_bao, h->qsr ? 1 : 0, 1 + (int32_t)h->peers.size(), theta, S, block, thresholds, n_thr,
+                             sample, chi2_blocks, acc);
+}
+
+extern "C" int cf_resid_sigma(cf_handle* h, int32_t block, double* out) {
+  if (!h || !out) return cf_set_error(CF_ERR_INVALID, "cf_resid_sigma: null argument");
+  if (block != CF_RB_SN && block != CF_RB_BAO) return cf_set_error(CF_ERR_INVALID, "cf_resid_sigma: block must be CF_RB_SN or CF_RB_BAO");
+  const std::vector<double>& s = block == CF_RB_SN ? h->sigma_sn_host : h->sigma_bao_host;
+  if (h->qsr || s.empty()) return cf_set_error(CF_ERR_INVALID, "cf_resid_sigma: this likelihood has no such block");
+  memcpy(out, s.data(), s.size() * 8);
+  return CF_OK;
+}
+
+extern "C" int cf_resid_set_chunk(cf_handle* h, int64_t rows) { return set_chunk(h, &cf_handle::resid_chunk, rows, "cf_resid_set_chunk"); }
+
+// Buffers for chunks of `rows` rows and the device copy of sigma.  Growing frees buffers an evaluation on a caller's stream may
+// still use: synchronise first, as ensure_workspace does.
+int resid_prepare(const HandleScope& hs, int64_t rows) {
+  cf_handle* const h = hs.h;
+  if (!h->sigma_uploaded) {
+    int rc;
+    if (!h->sigma_sn_host.empty() && (rc = upload(h->sigma_sn, h->sigma_sn_host.data(), (int64_t)h->sigma_sn_host.size()))) return rc;
+    if (!h->sigma_bao_host.empty() && (rc = upload(h->sigma_bao, h->sigma_bao_host.data(), (int64_t)h->sigma_bao_host.size()))) return rc;
+    h->sigma_uploaded = true;
+  }
+  if (rows <= h->resid_rows) return 0;
+  HIP_TRY(hipDeviceSynchronize());
+  const int64_t n = h->d.n_sn, nb = h->d.n_bao;
+  if (n > 0 && h->r_mc.ensure((size_t)rows * n * 8)) return CF_ERR_HIP;
+  if (nb > 0 && h->r_bt.ensure((size_t)rows * nb * 8)) return CF_ERR_HIP;
+  if (h->r_blk.ensure((size_t)rows * 8 * 8) || h->r_snb.ensure((size_t)rows * 8) || h->r_fsb.ensure((size_t)rows * 8)) return CF_ERR_HIP;
+  h->resid_rows = rows;
+  return 0;
+}
+
+// Arguments checked.  Device pointers throughout.
+static int resid_run(const HandleScope& hs, const double* d_theta, int64_t S, const double* d_w, int32_t block,
+                     const double* thresholds, int32_t n_thr, double* d_sample, double* d_chi2_blocks, const cf_resid_acc* acc,
+                     hipStream_t st) {
+  cf_handle* const h = hs.h;
+  int rc;
+  const int64_t chunk = std::min<int64_t>(S, h->resid_chunk > 0 ? h->resid_chunk : CF_RESID_CHUNK);
+  if ((rc = ensure_workspace(h, chunk))) return rc;
+  if ((rc = resid_prepare(hs, chunk))) return rc;
+  const cf_dev_desc& d = h->d;
+  const bool want_blocks = d_chi2_blocks != nullptr;
+  cf_resid_src src{};
+  if (block == CF_RB_SN) {
+    src.rows = h->delta.as<const double>();
+    src.data = d.obs;
+    src.mu_corr = h->r_mc.as<const double>();
+    src.sigma = h->sigma_sn.as<const double>();
+    src.pitch = d.n_ld;
+    src.n = d.n_sn;
+    src.bao = 0;
+  } else {
+    src.rows = h->r_bt.as<const double>();
+    src.data = d.bao_val;
+    src.mu_corr = nullptr;
+    src.sigma = h->sigma_bao.as<const double>();
+    src.pitch = d.n_bao;
+    src.n = d.n_bao;
+    src.bao = 1;
+  }
+  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+    const int64_t m = std::min(chunk, S - s0);
+    if (want_blocks) {  // a block the likelihood lacks keeps 0, as in cf_eval_parts
+      HIP_TRY(hipMemsetAsync(h->r_snb.p, 0, (size_t)m * 8, st));
+      HIP_TRY(hipMemsetAsync(h->r_fsb.p, 0, (size_t)m * 8, st));
+      HIP_TRY(hipMemsetAsync(h->r_blk.p, 0, (size_t)m * 8 * 8, st));
+    }
+    // a mu_corr buffer selects the accessor form of the per-walker kernel (the reference's exact sequence, rows in row layout)
+    if ((rc = launch_path(h, d_theta + s0 * d.ndim, m, h->out.as<double>(), CF_OUT_CHI2, st, nullptr,
+                          d.n_sn > 0 ? h->r_mc.as<double>() : nullptr, want_blocks ? h->r_blk.as<double>() : nullptr,
+                          d.n_bao > 0 ? h->r_bt.as<double>() : nullptr, want_blocks ? h->r_snb.as<double>() : nullptr,
+                          want_blocks ? h->r_fsb.as<double>() : nullptr, nullptr)))
+      return rc;
+    cf_resid_blocks blk{h->r_snb.as<const double>(), h->r_blk.as<const double>(), h->r_fsb.as<const double>(),
+                        want_blocks ? d_chi2_blocks + 10 * s0 : nullptr};
+    if ((rc = cf_resid_launch(src, m, d_sample ? d_sample + (int64_t)CF_RS_NCOL * s0 : nullptr, blk, d_w ? d_w + s0 : nullptr, thresholds,
+                              n_thr, acc, st)))
+      return rc;
+  }
+  return CF_OK;
+}
+
+extern "C" int cf_resid_device(cf_handle* h, const double* d_theta, int64_t S, const double* d_w, int32_t block, const double* thresholds,
+                               int32_t n_thr, double* d_sample, double* d_chi2_blocks, cf_resid_acc* acc, void* hip_stream) {
+  int rc = resid_check(h, d_theta, S, block, thresholds, n_thr, d_sample, d_chi2_blocks, acc);
+  if (rc) return rc;
+  if (S == 0) return CF_OK;
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  return resid_run(hs, d_theta, S, d_w, block, thresholds, n_thr, d_sample, d_chi2_blocks, acc, (hipStream_t)hip_stream);
+}
+
+// Host-buffer twin: rows in pieces through temporary device buffers on the handle's own stream; the accumulator goes to the
+// device once, is continued there piece by piece, and comes back at the end.
+
+extern "C" int cf_resid(cf_handle* h, const double* theta, int64_t S, const double* w, int32_t block, const double* thresholds,
+                        int32_t n_thr, double* sample, double* chi2_blocks, cf_resid_acc* acc) {
+  int rc = resid_check(h, theta, S, block, thresholds, n_thr, sample, chi2_blocks, acc);
+  if (rc) return rc;
+  if (S == 0) return CF_OK;
+  HandleScope hs(h);
+  HIP_TRY(hs.err);
+  RowStage rows(h->stream, std::min<int64_t>(S, CF_RESID_HOST_PIECE));
+  const double* dth = rows.in(theta, (size_t)h->d.ndim * 8);
+  const double* dw = rows.in(w, 8);
+  double* ds = rows.out(sample, (size_t)CF_RS_NCOL * 8);
+  double* db = rows.out(chi2_blocks, 10 * 8);
+  HostAccTwin dacc;
+  if ((rc = dacc.up(acc, h->stream))) return rc;
+  if ((rc = rows.run(S, [&](int64_t, int64_t m) {
+         return resid_run(hs, dth, m, dw, block, thresholds, n_thr, ds, db, dacc.ptr(), h->stream);
+       })))
+    return rc;
+  return dacc.down();
+}
+
+// sqrt of the diagonal of inverse(inv_cov) (Gauss-Jordan with partial pivoting in extended precision): the errors of the BAO data
+// as the fit report plots them.  A singular matrix gives NaN.
+void resid_bao_sigma(const double* inv_cov, int n, std::vector<double>& out) {
+  std::vector<long double> a((size_t)n * 2 * n, 0.0L);
+  const int ld = 2 * n;
+  for (int i = 0; i < n; ++i) {
+    for (int j = 0; j < n; ++j) a[(size_t)i * ld + j] = inv_cov[(size_t)i * n + j];
+    a[(size_t)i * ld + n + i] = 1.0L;
+  }
+  bool ok = true;
+  for (int k = 0; k < n && ok; ++k) {
+    int p = k;
+    for (int i = k + 1; i < n; ++i)
+      if (fabsl(a[(size_t)i * ld + k]) > fabsl(a[(size_t)p * ld + k])) p = i;
+    if (!(fabsl(a[(size_t)p * ld + k]) > 0.0L) || !std::isfinite((double)a[(size_t)p * ld + k])) { ok = false; break; }
+    if (p != k)
+      for (int j = 0; j < ld; ++j) std::swap(a[(size_t)p * ld + j], a[(size_t)k * ld + j]);
+    const long double inv = 1.0L / a[(size_t)k * ld + k];
+    for (int j = 0; j < ld; ++j) a[(size_t)k * ld + j] *= inv;
+    for (int i = 0; i < n; ++i) {
+      if (i == k) continue;
+      const long double f = a[(size_t)i * ld + k];
+      if (f != 0.0L)
+        for (int j = 0; j < ld; ++j) a[(size_t)i * ld + j] -= f * a[(size_t)k * ld + j];
+    }
+  }
+  out.assign((size_t)n, std::nan(""));
+  if (ok)
+    for (int i = 0; i < n; ++i) out[(size_t)i] = (double)sqrtl(a[(size_t)i * ld + n + i]);
+}
+
+// sqrt(C_ii) = |row i of L| of the SN data: the factor is not kept on the host.
+void resid_sn_sigma(const double* L, int64_t n, int64_t ld, std::vector<double>& out) {
+  out.resize((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    long double acc = 0.0L;
+    const double* row = L + i * ld;
+    for (int64_t j = 0; j <= i; ++j) acc += (long double)row[j] * row[j];
+    out[(size_t)i] = (double)sqrtl(acc);
+  }
 }

@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import create_refusals
 from conftest import ROOT, golden
 
 HEADER = os.path.join(ROOT, "include", "cosmofit.h")
@@ -102,6 +103,18 @@ def test_descriptor_validation(pkg):
         pkg.LikelihoodEngine(ndim=2, z_max=1.0, params=dict(H0=pkg.Param(5)))
     with pytest.raises(ValueError):
         pkg.LikelihoodEngine(ndim=2, z_max=1.0, params=dict(bogus=pkg.Param(0)))
+    # the refusals that need a look at the descriptor's arrays: bounds, the Gaussian terms' indices, the factor's pivots
+    create_refusals.check(pkg)
+
+
+def test_create_quasar_refuses_a_device_list_before_any_device_work(pkg):
+    import quasar_shapes as qs
+
+    kw = qs.engine_kwargs(qs.build_case(0), pkg.Param, pkg.engine.solve_mode_of("auto"))
+    with pytest.raises(pkg.CosmofitError) as err:
+        pkg.LikelihoodEngine(devices=[0], **kw)
+    assert err.value.code == -5
+    assert str(err.value) == "CF_ERR_UNSUPPORTED: cf_create_quasar: a quasar handle lives on one device (n_devices must be 0)"
 
 
 @pytest.mark.parametrize("n", [1, 15, 16, 17, 129, 256, 257, 300, 531])
