@@ -352,6 +352,14 @@ EXPORTS = {
     "cf_group_quad_device": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _VP]),
     "cf_reweight_check_args": (C.c_int, [_VP, _I64, _I64, _I32, _VP, _I64, _I32, _VP, _VP]),
     "cf_reweight_device": (C.c_int, [_VP, _I64, _I64, _I32, _VP, _VP, _I64, _I32, _VP, _VP, _VP]),
+    "cf_rep_check_args": (C.c_int, [_I64, _I64, _I32, _I32, _I32, _I32, _I32]),
+    "cf_rep_key": (C.c_uint64, [C.c_uint64, C.c_uint64, _I32, _I32]),
+    "cf_rep_kde_prepare": (C.c_int, [_VP, _I64, _I64, _I32, _I32, _I32, _VP, C.c_uint64, _I32, _VP, _VP, _VP]),
+    "cf_rep_propose": (C.c_int, [_I32, _VP, _I64, _I64, _I32, _I32, _I32, _VP, C.c_uint64, _I32, C.c_double, C.c_double, _VP, _VP,
+                                 _VP, _VP, _VP]),
+    "cf_rep_accept_record": (C.c_int, [_VP, _VP, _VP, _I64, _I64, _I32, _I32, _I32, _VP, C.c_uint64, _I32, _VP, _VP, _VP, _VP, _VP,
+                                       _VP, _VP, _VP, _VP, _VP]),
+    "cf_rep_swap": (C.c_int, [_VP, _VP, _I64, _I32, _I64, _I32, _VP, _VP, C.c_uint64, _I32, _VP, _VP]),
 }
 
 

@@ -515,6 +515,50 @@ int cf_ens_accept_record(const int64_t* d_ids, const int64_t* d_local_idx, int64
                          double* d_logp_local, uint64_t* d_n_accepted, double* d_chain_slot, double* d_logp_slot,
                          int64_t* d_walker_accepted, void* hip_stream);
 
+/* ---- Replica ensembles (csrc/cosmofit_replica.hip): R independent ensembles of w walkers each, stepped together by the
+ * launches of one split update, with an optional inverse temperature per replica and swaps between the rungs of a ladder.
+ * All pointers are device pointers on the current device, all launches are asynchronous on `hip_stream`.
+ * Layout: d_pos [R * w * ndim], global row r w + l (replica r, local walker l); d_l [R * w] the walkers' log P (the
+ * log-LIKELIHOOD in a tempered run).  w is a multiple of n_splits, so every replica has n_act = w / n_splits active walkers per
+ * split and nc = w - n_act complementary ones; active row i = r n_act + m is the member of local group m of replica r that
+ * belongs to `split`.  Partners come from the walker's own replica only.
+ * Random numbers: d_base [R], base_r = mix(seeds[r] * 0x9E3779B97F4A7C15 + 0x5851F42D4C957F2D) (splitmix64 finaliser), uploaded
+ * once; the kernels form the keys of ensemble.py's stream_key(seeds[r], step, split, stream) = mix(base_r ^ step) + (split << 8)
+ * + stream themselves (no per-step upload), the counter is the local index l, and the split key is stream 254 of (step, 0), or 0
+ * for randomize = 0.  Replica r is therefore, bit for bit, the chain of a stand-alone ensemble (cf_ens_*) with seed seeds[r]: the
+ * per-element arithmetic and the reduction orders are the same device code.
+ *   cf_rep_check_args: HOST function (no device needed), the refusals every entry point applies before it launches: R >= 1,
+ *     w even and >= 4, w divisible by n_splits, nc > ndim for kind 2 (KDE), ndim in 1..16, R w < 2^31; T = 0 (no tempering) or
+ *     the rungs of a ladder (R a multiple of T, has_bounds required).  CF_ERR_INVALID with the reason in cf_last_error.
+ *   cf_rep_key: HOST function, the 64-bit key the kernels form from (base, step, split, stream).
+ *   cf_rep_kde_prepare: one 256-thread workgroup per replica; d_params [R * (2 ndim^2 + 1)], d_wc [R * nc * ndim], per replica
+ *     as cf_ens_kde_prepare.
+ *   cf_rep_propose: kind as cf_ens_propose; d_y [R * n_act * ndim], d_log_factor [R * n_act]; for the KDE move the log-factor
+ *     kernel follows in the same call.
+ *   cf_rep_accept_record: accept with probability min(1, exp((log_factor + beta l_new) - beta l_old)), beta = d_beta[r] (null:
+ *     1, which is cf_ens_accept's expression to the bit); NaN never accepts; with d_lo / d_hi [ndim] (both null: no box) a
+ *     proposal that is not strictly inside the box never accepts.  d_beta needs the box.  Adds the accepted moves of replica r to
+ *     d_n_accepted[r]; d_chain_slot [R * w * ndim] / d_l_slot [R * w] / d_walker_accepted [R * w] as in cf_ens_accept_record
+ *     (slots both null or both set, counts may be null).
+ *   cf_rep_swap: R = C T replicas, r = c T + t: for every ladder c and every rung t = parity, parity + 2, ... with t + 1 < T,
+ *     walker l of rung t and walker l of rung t + 1 exchange rows and d_l exactly when
+ *     log u < (beta_t - beta_{t+1}) (l_{t+1,l} - l_{t,l}), u = the uniform of (stream_key(seeds[c T + t], step, 0, 253), counter
+ *     l), d_beta [R]; a NaN difference never swaps.  Adds the accepted swaps to d_n_swapped [C * (T - 1)] at c (T - 1) + t. */
+int cf_rep_check_args(int64_t R, int64_t w, int32_t ndim, int32_t n_splits, int32_t kind, int32_t T, int32_t has_bounds);
+uint64_t cf_rep_key(uint64_t base, uint64_t step, int32_t split, int32_t stream);
+int cf_rep_kde_prepare(const double* d_pos, int64_t R, int64_t w, int32_t ndim, int32_t n_splits, int32_t split,
+                       const uint64_t* d_base, uint64_t step, int32_t randomize, double* d_params, double* d_wc, void* hip_stream);
+int cf_rep_propose(int32_t kind, const double* d_pos, int64_t R, int64_t w, int32_t ndim, int32_t n_splits, int32_t split,
+                   const uint64_t* d_base, uint64_t step, int32_t randomize, double a, double de_sigma, const double* d_params,
+                   const double* d_wc, double* d_y, double* d_log_factor, void* hip_stream);
+int cf_rep_accept_record(const double* d_y, const double* d_l_new, const double* d_log_factor, int64_t R, int64_t w, int32_t ndim,
+                         int32_t n_splits, int32_t split, const uint64_t* d_base, uint64_t step, int32_t randomize,
+                         const double* d_beta, const double* d_lo, const double* d_hi, double* d_pos, double* d_l,
+                         uint64_t* d_n_accepted, double* d_chain_slot, double* d_l_slot, int64_t* d_walker_accepted,
+                         void* hip_stream);
+int cf_rep_swap(double* d_pos, double* d_l, int64_t C, int32_t T, int64_t w, int32_t ndim, const double* d_beta,
+                const uint64_t* d_base, uint64_t step, int32_t parity, uint64_t* d_n_swapped, void* hip_stream);
+
 /* ---- chain statistics (csrc/cosmofit_chain.hip): emcee's integrated autocorrelation time by direct lag sums ----------------
  * A chain is [n_t, n_s] float64 in device memory, n_s = n_walkers * ndim series side by side (row t holds every series at
  * step t: an emcee chain [n_t, n_w, ndim] as it lies in memory).  Every sum runs in a fixed order (no atomics), so the
