@@ -209,6 +209,9 @@ class cf_infl_out(C.Structure):
                 ("g", C.c_void_p), ("contrib", C.c_void_p), ("z", C.c_void_p), ("loo", C.c_void_p), ("sample", C.c_void_p)]
 
 
+CF_CSCALE_MAX_S, CF_CSCALE_CHUNK = 16, 4096
+
+
 CF_BRIDGE_MAX_NDIM, CF_BRIDGE_SLICE, CF_BRIDGE_RESULT_DOUBLES = 16, 2048, 8
 # cf_bridge_result of include/cosmofit.h, in index order, and cf_bridge_status
 BRIDGE_RESULT = ("log_r", "n_iter", "status", "mean_f1", "var_f1", "mean_f2", "var_f2", "r")
@@ -339,6 +342,15 @@ EXPORTS = {
     "cf_infl_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _VP, _I64, _I32, _VP, _I32,
                                      C.POINTER(cf_infl_out), C.POINTER(cf_resid_acc), C.POINTER(cf_resid_acc)]),
     "cf_infl_set_chunk": (C.c_int, [_VP, _I64]),
+    "cf_cscale_create": (C.c_int, [_VP, _I64, _I64, _VP, _I32, C.POINTER(_VP)]),
+    "cf_cscale_destroy": (None, [_VP]),
+    "cf_cscale_look": (C.c_int, [_VP, C.POINTER(_I64), C.POINTER(_I32)]),
+    "cf_cscale_apply_device": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I32, _VP, _VP, _VP, _VP]),
+    "cf_cscale_eval_device": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I64, _I32, _VP, _VP, _VP]),
+    "cf_cscale_eval": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I64, _I32, _VP, _VP]),
+    "cf_cscale_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I64, _I32, _VP, _VP, _I32, _I64, _I32, _VP, _VP]),
+    "cf_cscale_set_chunk": (C.c_int, [_VP, _I64]),
+    "cf_selftest_cscale_host": (C.c_int, [_VP, _VP, _I64, _VP, _I32, _VP, _VP]),
     "cf_bridge_forward": (C.c_int, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cf_bridge_points": (C.c_int, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
     "cf_bridge_draw": (C.c_int, [C.c_uint64, _I64, _I64, _I32, _VP, _VP]),

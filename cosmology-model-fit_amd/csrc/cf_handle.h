@@ -140,6 +140,7 @@ struct cf_handle {
   // each [rows][n] and allocated when first needed; rows per chunk (0: CF_INFL_CHUNK).  The residual rows are the fit report's.
   DevBuf i_g, i_contrib, i_z;
   int64_t infl_chunk = 0;
+  int64_t cscale_chunk = 0;  // rows per chunk of cf_cscale_eval_device (0: CF_CSCALE_CHUNK); residual rows and chi^2 shares are the fit report's
 };
 
 // An entry point's hold on its handle: h->mu locked and the handle's device current (cf_host.h: DeviceScope) until it returns.

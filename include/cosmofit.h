@@ -1200,6 +1200,78 @@ int cf_infl_check_args(int64_t n_sn, int32_t n_bao, int32_t is_quasar, int32_t n
  * results do not depend on it: it exists so that tests can cross chunk boundaries with few rows. */
 int cf_infl_set_chunk(cf_handle* h, int64_t rows);
 
+/* ---- A free amplitude on the SN covariance: C(s) = C0 + s C1 (csrc/cosmofit_cscale.hip; the driver is
+ * cosmology-model-fit_amd/covscale.py) -----------------------------------------------------------------------------------------
+ * The handle holds ONE Cholesky factor, C0 = L0 L0^T, fixed at cf_create.  One scalar amplitude on a second matrix needs no new
+ * factor: with A = L0^-1 C1 L0^-T = Q diag(lambda) Q^T and T = Q^T L0^-1 (both formed once, on the host, by the caller:
+ * covscale.decompose), a residual row r gives y = T r and
+ *   quad(s)   = r^T C(s)^-1 r      = sum_k y_k^2 / (1 + s lambda_k)
+ *   logdet(s) = ln|C(s)| - ln|C0|  = sum_k log1p(s lambda_k)
+ * valid while 1 + s lambda_k > 0 for every k.  C1: the identity (intrinsic scatter, s = sigma_int^2), a 0/1 diagonal (the scatter
+ * of one survey or redshift range), a systematics matrix, any symmetric matrix (negative eigenvalues only bound s).
+ *
+ * cf_cscale: T and lambda on one device.  cf_cscale_create reads T [n x n, row pitch ld] and lambda [n] and uploads M = T^T,
+ * zero-padded to a multiple of 16, and lambda.  CF_ERR_INVALID: a null argument, n < 1 or > 32768, ld < n, a non-finite entry of
+ * T or lambda; CF_ERR_NO_DEVICE without a device.  cf_cscale_look reports n and the device (either pointer may be NULL).
+ *
+ * cf_cscale_apply_device: the kernels alone, on caller-supplied rows.  For row s < S and j < n_s, with amplitude
+ * d_s[s * n_s + j], it writes d_quad[s * n_s + j] and d_logdet[s * n_s + j] (either may be NULL); d_y is [S * n] = T r, or NULL
+ * to never store y (the product Y = R M runs on FP64 matrix cores and the first reduction of quad is fused into its epilogue).
+ * Columns >= n and rows >= S of d_rows (row pitch `pitch` >= n) are never read: a select, not a product with zero.
+ * 1 <= n_s <= CF_CSCALE_MAX_S.  CF_ERR_INVALID: a null cf_cscale, S < 0 or > 2^31 - 1, n_s out of range, pitch < n, no output at
+ * all, and (S > 0) null rows or amplitudes.  S = 0 is a no-op.
+ *
+ * cf_cscale_eval_device: for every row of d_theta [S * ndim] the residual row of the accessor path (as cf_infl_device: chunks of
+ * at most CF_CSCALE_CHUNK rows into the handle's workspace), then the product and the row kernel.  d_out [S * n_s] by out_kind:
+ *   CF_OUT_CHI2              the engine's chi^2 of the row with its SN term replaced by quad: (chi2 - chi2_SN(C0)) + quad
+ *   CF_OUT_LOGL / CF_OUT_LOGP  the engine's own value of that kind plus 0.5 chi2_SN(C0) - 0.5 (quad + logdet)
+ * chi2_SN(C0) is the SN chi^2 the engine computed for that row, so every other block, constant and prior term stays what the
+ * engine makes it.  d_parts: NULL, or [S * n_s * 2] holding (quad, logdet).
+ *
+ * Domain and special values, per (row, j), never leaking to a neighbour: 1 + s lambda_k <= 0 for any k gives NaN in quad and
+ * logdet, -inf in d_out for LOGL / LOGP and NaN for CHI2; a non-finite s or a non-finite theta entry gives NaN in that row's
+ * outputs only; where the engine's own LOGL / LOGP is -inf (outside the prior box, a non-finite chi^2) d_out is -inf; s = 0
+ * gives logdet exactly 0.0 and quad = sum_k y_k^2 in the kernel's order; a zero row gives exact zeros.
+ *
+ * Determinism: the outputs for (row, s_j) depend on that row's theta (its residual row), on s_j, on T and on lambda only -- not
+ * on S or the row's position, not on n_s or the other amplitudes of the row, not on the chunking (cf_cscale_set_chunk), device or
+ * host pointers, the stream or repetition.  One accumulator per element of y, an ascending k loop over ceil(n / 32) * 32 columns,
+ * quad summed per 32-column slab in a fixed lane order and the slabs in ascending order, logdet as 64 lane-strided partials and
+ * a fixed butterfly; no atomics.
+ *
+ * Checks of the eval entry points, all before the first HIP call (cf_cscale_check_args states them without a handle), all
+ * CF_ERR_INVALID: a quasar handle, a handle over several devices, no SN block, a null cf_cscale, a cf_cscale whose n is not n_sn
+ * or that lives on another device, S < 0 or > 2^31 - 1, n_s out of range, an out_kind that is none of the three, no output at
+ * all, and (S > 0) a null d_theta or d_s.  S = 0 is a no-op.
+ * Stream contract: that of cf_resid_device (the handle's ONE workspace); a cf_cscale has ONE scratch for the slab partials, so a
+ * call on another stream than the previous call on the same cf_cscale first waits, on the host, for the device.
+ * cf_cscale_eval: the same on host buffers, synchronous, same bits. */
+#define CF_CSCALE_MAX_S 16
+#define CF_CSCALE_CHUNK 4096
+typedef struct cf_cscale cf_cscale;
+int cf_cscale_create(const double* T, int64_t n, int64_t ld, const double* lambda, int32_t device, cf_cscale** out);
+void cf_cscale_destroy(cf_cscale* p);
+int cf_cscale_look(const cf_cscale* p, int64_t* n, int32_t* device);
+int cf_cscale_apply_device(cf_cscale* p, const double* d_rows, int64_t pitch, int64_t S, const double* d_s, int32_t n_s,
+                           double* d_quad, double* d_logdet, double* d_y, void* hip_stream);
+int cf_cscale_eval_device(cf_handle* h, cf_cscale* p, const double* d_theta, const double* d_s, int32_t n_s, int64_t S,
+                          int32_t out_kind, double* d_out, double* d_parts, void* hip_stream);
+int cf_cscale_eval(cf_handle* h, cf_cscale* p, const double* theta, const double* s, int32_t n_s, int64_t S, int32_t out_kind,
+                   double* out, double* parts);
+/* The argument rules above as host arithmetic on the facts of a handle (its n_sn, whether it is a quasar handle, its number of
+ * devices, its device) and of a cf_cscale (has_cscale: non-null; its n and device).  No handle and no device needed. */
+int cf_cscale_check_args(int64_t n_sn, int32_t is_quasar, int32_t n_devices, int32_t handle_device, int32_t has_cscale,
+                         int64_t cscale_n, int32_t cscale_device, const void* theta, const void* s, int32_t n_s, int64_t S,
+                         int32_t out_kind, const void* out, const void* parts);
+/* Rows per chunk of the following cf_cscale_eval_device / cf_cscale_eval calls of this handle, 1 .. 65536; 0 restores
+ * CF_CSCALE_CHUNK.  The results do not depend on it: it exists so that tests can cross chunk boundaries with few rows. */
+int cf_cscale_set_chunk(cf_handle* h, int64_t rows);
+/* The arithmetic of the row kernel and of the product's epilogue compiled for the host, in the same order of operations (one
+ * __host__ __device__ function per term, shared with the kernels): quad [n_s] and logdet [n_s] (either may be NULL) of one row
+ * y [n] for the amplitudes s [n_s], with the domain rule.  No device needed. */
+int cf_selftest_cscale_host(const double* y, const double* lambda, int64_t n, const double* s, int32_t n_s, double* quad,
+                            double* logdet);
+
 /* ---- Bridge-sampling evidence (csrc/cosmofit_bridge.hip; the driver is cosmology-model-fit_amd/evidence.py) ----------------
  * ln Z of a posterior in a finite box from a chain and draws of a Gaussian fitted to it in unbounded coordinates (Meng & Wong
  * 1996; Gronau et al. 2017).  Everything is float64, row-major, device pointers on the current device, asynchronous on
