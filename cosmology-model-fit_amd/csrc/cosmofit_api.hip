@@ -414,6 +414,13 @@ int validate_desc(const cf_desc* c) {
     if (c->gauss[g].idx < 0 || c->gauss[g].idx >= c->ndim) return fail(CF_ERR_INVALID, "cf_create: gauss idx");
   for (int g = 0; g < c->n_chi2_gauss; ++g)
     if (c->chi2_gauss[g].idx < 0 || c->chi2_gauss[g].idx >= c->ndim) return fail(CF_ERR_INVALID, "cf_create: chi2_gauss idx");
+  // sigma 0 with theta on the mean is 0 / 0 in the epilogue: a NaN that is neither mapped to -inf nor counted
+  for (int g = 0; g < c->n_gauss; ++g)
+    if (c->gauss[g].sigma == 0.0 || !std::isfinite(c->gauss[g].sigma))
+      return fail(CF_ERR_INVALID, "cf_create: gauss sigma must be finite and non-zero");
+  for (int g = 0; g < c->n_chi2_gauss; ++g)
+    if (c->chi2_gauss[g].sigma == 0.0 || !std::isfinite(c->chi2_gauss[g].sigma))
+      return fail(CF_ERR_INVALID, "cf_create: chi2_gauss sigma must be finite and non-zero");
   for (int64_t i = 0; i < c->n_sn; ++i) {
     const double piv = c->sn_chol[i * c->sn_chol_ld + i];
     if (!(piv > 0.0) || !std::isfinite(piv))

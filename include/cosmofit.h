@@ -152,7 +152,8 @@ typedef struct cf_gauss_prior {
   int32_t idx;   /* theta index */
   int32_t _pad;
   double mean;
-  double sigma;  /* term: -0.5*(theta[idx]-mean)^2/sigma^2        sn/pantheon.py:85 */
+  double sigma;  /* term: -0.5*(theta[idx]-mean)^2/sigma^2        sn/pantheon.py:85
+                    zero or not finite: refused by cf_create (CF_ERR_INVALID) */
 } cf_gauss_prior;
 
 /*

@@ -1,5 +1,5 @@
-"""The four descriptor refusals cf_create makes from the descriptor alone (validate_desc: bounds, the two Gaussian-term index
-ranges, the factor's pivots), as ``LikelihoodEngine`` keywords: one list for tests/test_abi_cpu.py (no device) and
+"""The descriptor refusals cf_create makes from the descriptor alone (validate_desc: bounds, the two Gaussian-term index
+ranges and their sigmas, the factor's pivots), as ``LikelihoodEngine`` keywords: one list for tests/test_abi_cpu.py (no device) and
 tests/test_gpu_create_refusals.py (between two working engines).  The engine pre-checks none of them."""
 import re
 
@@ -21,6 +21,11 @@ def cases(Param):
         ("bounds lo == hi", dict(bounds=[[60.0, 80.0], [0.3, 0.3]]), "CF_ERR_INVALID: cf_create: bounds must satisfy lo < hi"),
         ("gauss idx == ndim", dict(gauss=[(2, 0.0, 1.0)]), "CF_ERR_INVALID: cf_create: gauss idx"),
         ("chi2_gauss idx == ndim", dict(chi2_gauss=[(2, 0.0, 1.0)]), "CF_ERR_INVALID: cf_create: chi2_gauss idx"),
+        ("gauss sigma == 0", dict(gauss=[(1, 0.3, 0.0)]), "CF_ERR_INVALID: cf_create: gauss sigma must be finite and non-zero"),
+        ("gauss sigma inf", dict(gauss=[(0, 70.0, 1.0), (1, 0.3, np.inf)]), "CF_ERR_INVALID: cf_create: gauss sigma must be finite and non-zero"),
+        ("chi2_gauss sigma == 0", dict(chi2_gauss=[(0, 70.0, 1.0), (1, 0.3, -0.0)]),
+         "CF_ERR_INVALID: cf_create: chi2_gauss sigma must be finite and non-zero"),
+        ("chi2_gauss sigma NaN", dict(chi2_gauss=[(1, 0.3, np.nan)]), "CF_ERR_INVALID: cf_create: chi2_gauss sigma must be finite and non-zero"),
         ("zero pivot", dict(sn=_sn2(0.0)), PIVOT),
         ("NaN pivot", dict(sn=_sn2(np.nan)), PIVOT),
     ]
