@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import on_device, stream_of
 
 _FIRST_LAGS = 64   # lags of the first pass; every further pass doubles the range ...
 _MAX_PASS = 512    # ... by at most this many lags (the pass's lag sums are [lags, n_walkers * ndim] doubles)
@@ -33,17 +34,9 @@ class AutocorrError(Exception):
         super().__init__(*args, **kwargs)
 
 
-def _on_device(x: torch.Tensor, what: str) -> torch.Tensor:
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError(f"{what} takes a tensor on an MI355X (there is no CPU implementation to fall back to)")
-    if x.dtype != torch.float64:
-        raise ValueError(f"{what} takes float64")
-    return x
-
-
 def _as_chain(x: torch.Tensor) -> torch.Tensor:
     """emcee's shapes: [n_t] -> [n_t, 1, 1], [n_t, n_w] -> [n_t, n_w, 1], [n_t, n_w, ndim] as is."""
-    x = _on_device(x, "integrated_time")
+    x = on_device(x, "integrated_time")
     if x.dim() == 1:
         x = x[:, None, None]
     elif x.dim() == 2:
@@ -68,7 +61,7 @@ def autocorr_window_search(x: torch.Tensor, c: float = 5.0):
     L = _lib
     lib = L.lib()
     with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
+        stream = stream_of(x.device)
         mean = torch.empty(n_s, dtype=torch.float64, device=x.device)
         L.check(lib.cf_chain_mean(x.data_ptr(), n_t, n_s, mean.data_ptr(), stream))
         c0 = None
@@ -121,7 +114,7 @@ def integrated_time(x: torch.Tensor, c: float = 5, tol: float = 50, quiet: bool 
 def gelman_rubin(chains: torch.Tensor) -> torch.Tensor:
     """The reference's ``gelman_rubin(chains)`` on a device tensor (M, N, D): per-"chain" variances (ddof 1) along axis 1,
     W = their mean over axis 0, B = N var(means, ddof 1), sqrt(((N - 1) / N W + B / N) / W); [D] on the device."""
-    chains = _on_device(chains, "gelman_rubin")
+    chains = on_device(chains, "gelman_rubin")
     if chains.dim() != 3:
         raise ValueError("gelman_rubin takes a 3-d chain")
     M, N, D = chains.shape
@@ -136,7 +129,7 @@ def percentile(samples: torch.Tensor, q) -> torch.Tensor:
     on the device; the virtual indices and weights are numpy's own scalar arithmetic; the interpolation is its ``_lerp``
     (a + (b - a) t, or b - (b - a)(1 - t) where t >= 0.5) as elementwise device operations.  Result [ndim] for a scalar q,
     [len(q), ndim] for a sequence (without the ndim axis for 1-d samples)."""
-    a = _on_device(samples, "percentile")
+    a = on_device(samples, "percentile")
     if a.dim() not in (1, 2) or a.shape[0] < 1:
         raise ValueError("percentile takes non-empty samples [n] or [n, ndim]")
     qs = np.true_divide(np.asarray(q, dtype=np.float64), np.float64(100))

@@ -34,13 +34,11 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib as L
+from ._args import ptr, stream_of
 
 PROBE_LIMIT = 1e-11  # the limit cf_create's pack probe uses
 MAX_S = L.CF_CSCALE_MAX_S
 
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _c1_matrix(C1, n: int) -> np.ndarray:
@@ -129,7 +127,7 @@ class Decomposition:
             raise ValueError("Decomposition takes T [n, n] and lam [n]")
         self.n, self.device = int(T.shape[0]), int(device)
         self._p = C.c_void_p()
-        L.check(L.lib().cf_cscale_create(_ptr(T), self.n, self.n, _ptr(lam), self.device, C.byref(self._p)))
+        L.check(L.lib().cf_cscale_create(ptr(T), self.n, self.n, ptr(lam), self.device, C.byref(self._p)))
 
     def close(self):
         if getattr(self, "_p", None) is not None and self._p.value:
@@ -162,10 +160,10 @@ class Decomposition:
         quad = torch.empty((S, n_s), **f64) if "quad" in want else None
         logdet = torch.empty((S, n_s), **f64) if "logdet" in want else None
         y = torch.empty((S, self.n), **f64) if want_y else None
-        ptr = lambda t: None if t is None else t.data_ptr()
+        dptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(rows.device):
-            L.check(L.lib().cf_cscale_apply_device(self._p, rows.data_ptr(), rows.stride(0), S, s.data_ptr(), n_s, ptr(quad),
-                                                   ptr(logdet), ptr(y), torch.cuda.current_stream(rows.device).cuda_stream))
+            L.check(L.lib().cf_cscale_apply_device(self._p, rows.data_ptr(), rows.stride(0), S, s.data_ptr(), n_s, dptr(quad),
+                                                   dptr(logdet), dptr(y), stream_of(rows.device)))
         return quad, logdet, y
 
 
@@ -253,7 +251,7 @@ class ScaledCovariance:
         W, n_s = s.shape
         out = np.empty((W, n_s))
         parts = np.empty((W, n_s, 2)) if want_parts else None
-        L.check(L.lib().cf_cscale_eval(self.engine._h, self._dec._p, _ptr(theta), _ptr(s), n_s, W, kind, _ptr(out), _ptr(parts)))
+        L.check(L.lib().cf_cscale_eval(self.engine._h, self._dec._p, ptr(theta), ptr(s), n_s, W, kind, ptr(out), ptr(parts)))
         return out, parts
 
     def _eval(self, theta_ext, kind):
@@ -301,7 +299,7 @@ class ScaledCovariance:
             with torch.cuda.device(theta.device):
                 L.check(L.lib().cf_cscale_eval_device(self.engine._h, self._dec._p, theta.data_ptr(), s.data_ptr(), s.shape[1],
                                                       theta.shape[0], kind, out.data_ptr(), None,
-                                                      torch.cuda.current_stream(theta.device).cuda_stream))
+                                                      stream_of(theta.device)))
         return out
 
     def torch_log_prob(self, kind: int = L.CF_OUT_LOGP):

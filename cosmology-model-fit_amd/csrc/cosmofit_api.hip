@@ -1378,8 +1378,7 @@ static int launch_eval(cf_handle* h, const double* th, int64_t Wc, double* out, 
     if (th_copy) th = th_copy;
     if (ev) HIP_TRY(hipEventRecord(ev[1], st));
   } else if (walker_work) {
-    // skewed {cum, dh} table: one spare 16-byte slot per 2^chunk_shift nodes
-    const size_t lds = ((size_t)d.n_grid + (d.n_grid >> d.chunk_shift) + 2) * 16;
+    const size_t lds = walker_lds_bytes(d.n_grid, d.chunk_shift);
     if (!dm_out && !mucorr_out && walker_fast_ok(d)) {  // the production form: lean kernel arguments, theta row across the lanes
       // a zero-copy evaluation reads theta from the pinned host block: the walker kernel leaves a copy of each row in device
       // memory and every later kernel of the evaluation (small blocks, growth, the solve's prior / output epilogue) reads THAT --
@@ -1408,7 +1407,7 @@ static int launch_eval(cf_handle* h, const double* th, int64_t Wc, double* out, 
     }
     if (h->has_growth)  // 256 lanes per walker: the growth ODE as a scan of 2 x 2 step matrices, the f sigma_8 quadratic form
       hipLaunchKernelGGL(pick_growth(d.ez_model, d.fde, d.fs8_steps), dim3((unsigned)Wc), dim3(256),
-                         (size_t)(2 * (d.fs8_steps + 1) + 16 + CF_MAX_FS8 + 2 + 256) * 8, st, d, th, Wc, (const d2*)bao_nodes, extra,
+                         growth_lds_bytes(d.fs8_steps), st, d, th, Wc, (const d2*)bao_nodes, extra,
                          h->has_small_blocks ? 1 : 0, fs8_block_out, fs8_theory_out);
   }
   if (ev) HIP_TRY(hipEventRecord(ev[2], st));
@@ -1718,7 +1717,7 @@ extern "C" int cf_eval_table(cf_handle* h, const double* theta, int64_t W, doubl
   DevBuf tab;
   if (tab.ensure((size_t)W * G * sizeof(d2))) return CF_ERR_HIP;
   HIP_TRY(hipMemcpyAsync(h->theta.p, theta, (size_t)W * d.ndim * 8, hipMemcpyHostToDevice, h->stream));
-  const size_t lds = ((size_t)G + (G >> d.chunk_shift) + 2) * 16;
+  const size_t lds = walker_lds_bytes(G, d.chunk_shift);
   hipLaunchKernelGGL(pick_walker(d.ez_model, d.fde), dim3((unsigned)W), dim3(512), lds, h->stream, d, h->theta.as<const double>(), W,
                      (double*)nullptr, (double*)nullptr, (double*)nullptr, (d2*)nullptr, tab.as<d2>());
   if (int launch_rc = cf_launch_status("cf_eval_table")) return launch_rc;
@@ -1775,11 +1774,11 @@ extern "C" int cf_eval_fs8_at(cf_handle* h, const double* theta, const double* z
     d.fs8_z = dz.as<const double>(); d.bao_base = dbase.as<const int32_t>(); d.fs8_step_of = dstep.as<const int32_t>();
     d.fs8_order = dorder.as<const int32_t>(); d.fs8_pts = dpts.as<const double>(); d.fs8_val = dval.as<const double>();
     d.fs8_inv_cov = dinv.as<const double>(); d.fs8_fid = dfid.as<const double>();
-    const size_t lds = ((size_t)d.n_grid + (d.n_grid >> d.chunk_shift) + 2) * 16;
+    const size_t lds = walker_lds_bytes(d.n_grid, d.chunk_shift);
     hipLaunchKernelGGL(pick_walker(d.ez_model, d.fde), dim3(1), dim3(512), lds, h->stream, d, h->theta.as<const double>(), (int64_t)1,
                        (double*)nullptr, (double*)nullptr, (double*)nullptr, nodes.as<d2>(), (d2*)nullptr);
     hipLaunchKernelGGL(pick_growth(d.ez_model, d.fde, d.fs8_steps), dim3(1), dim3(256),
-                       (size_t)(2 * (d.fs8_steps + 1) + 16 + CF_MAX_FS8 + 2 + 256) * 8, h->stream, d, h->theta.as<const double>(),
+                       growth_lds_bytes(d.fs8_steps), h->stream, d, h->theta.as<const double>(),
                        (int64_t)1, (const d2*)nodes.as<d2>(), extra.as<double>(), 0, (double*)nullptr, dout.as<double>());
     if (int launch_rc = cf_launch_status("cf_eval_fs8_at")) return launch_rc;
     HIP_TRY(hipMemcpyAsync(out + k0, dout.p, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1846,7 +1845,7 @@ extern "C" int cf_eval_bao_at(cf_handle* h, const double* theta, const double* z
     HIP_TRY(hipMemcpyAsync(dbase.p, base.data(), (size_t)m * 4, hipMemcpyHostToDevice, h->stream));
     d.bao_z = dz.as<const double>(); d.bao_qty = dq.as<const int32_t>(); d.bao_base = dbase.as<const int32_t>();
     d.bao_val = dval.as<const double>(); d.bao_inv_cov = dinv.as<const double>();
-    const size_t lds = ((size_t)d.n_grid + (d.n_grid >> d.chunk_shift) + 2) * 16;
+    const size_t lds = walker_lds_bytes(d.n_grid, d.chunk_shift);
     hipLaunchKernelGGL(pick_walker(d.ez_model, d.fde), dim3(1), dim3(512), lds, h->stream, d, h->theta.as<const double>(), (int64_t)1,
                        (double*)nullptr, (double*)nullptr, (double*)nullptr, nodes.as<d2>(), (d2*)nullptr);
     hipLaunchKernelGGL(pick_small_blocks(d.ez_model, d.fde, 16), dim3(1), dim3(256), 0, h->stream, d, h->theta.as<const double>(), (int64_t)1,

@@ -32,6 +32,7 @@
 
 #include "../../include/cosmofit.h"
 #include "cf_handle.h"
+#include "cf_wave.h"
 #include "cosmofit_resid.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -175,12 +176,6 @@ struct cf_cscale_row_args {
   int32_t n, n_s, n_slab, ndim, out_kind;
 };
 
-__device__ __forceinline__ double cscale_wave_sum(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-  return x;
-}
-
 __global__ void __launch_bounds__(CR_TPB) cscale_row_kernel(int64_t rows, cf_cscale_row_args a) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * CR_ROWS_PER_WG + (threadIdx.x >> 6);
@@ -193,7 +188,7 @@ __global__ void __launch_bounds__(CR_TPB) cscale_row_kernel(int64_t rows, cf_csc
     double ld = 0.0;
     bool bad = false;
     for (int k = lane; k < a.n; k += 64) ld += cscale_log_term(s, a.lam[k], &bad);
-    ld = cscale_wave_sum(ld);
+    ld = wave_sum(ld);
     bad = __any(bad);
     if (lane == j) { my_s = s; my_logdet = ld; my_bad = bad; }
   }
@@ -255,7 +250,7 @@ extern "C" int cf_selftest_cscale_host(const double* y, const double* lambda, in
       }
       q += v[0];
     }
-    // logdet: 64 lane-strided partials, then the butterfly (32, .., 1)
+    // logdet: 64 lane-strided partials, then the butterfly (32, .., 1) of wave_sum (cf_wave.h), written out on the host
     double v[64];
     bool bad = false;
     for (int l = 0; l < 64; ++l) {

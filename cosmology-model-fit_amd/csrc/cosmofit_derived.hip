@@ -213,10 +213,6 @@ struct DqTable {
   __device__ __forceinline__ d2 at(int g) const { return tab[g + (g >> chs)]; }
 };
 
-__device__ __forceinline__ double dq_grid_z(int i, int G, double step, double z_max) {  // np.linspace(0, z_max, G)[i]
-  return i == G - 1 ? z_max : (double)i * step;
-}
-
 // Cubic Hermite (nodes cum_dm, slopes dh), interval x[i] < xi <= x[i+1], linear extrapolation outside: interpolator.py:71-108
 __device__ __forceinline__ double dq_hermite(const DqTable& T, double xi) {
   const int G = T.G;
@@ -235,11 +231,11 @@ __device__ __forceinline__ double dq_hermite(const DqTable& T, double xi) {
     --i;
     x0 = (double)i * T.step;
   }
-  double x1 = dq_grid_z(i + 1, G, T.step, T.z_max);
+  double x1 = grid_z(i + 1, G, T.step, T.z_max);
   if (x1 < xi) {  // then i + 1 <= G - 2 because xi < z_max
     ++i;
     x0 = x1;
-    x1 = dq_grid_z(i + 1, G, T.step, T.z_max);
+    x1 = grid_z(i + 1, G, T.step, T.z_max);
   }
   const double h_i = x1 - x0;
   const double t = (xi - x0) * (i == G - 2 ? T.inv_last : T.inv_step);
@@ -258,7 +254,7 @@ __device__ __forceinline__ double dq_sgn(double v) { return (double)((v > 0) - (
 
 __device__ double dq_pchip_slope(const DqTable& T, int i) {
   const int n = T.G;
-  auto X = [&](int k) { return dq_grid_z(k, n, T.step, T.z_max); };
+  auto X = [&](int k) { return grid_z(k, n, T.step, T.z_max); };
   auto Y = [&](int k) { return T.at(k).y; };
   if (i > 0 && i < n - 1) {
     const double hl = X(i) - X(i - 1), hr = X(i + 1) - X(i);
@@ -289,23 +285,17 @@ __device__ double dq_pchip_dh(const DqTable& T, double xi) {
   if (xi >= T.z_max) return T.at(G - 1).y;
   int i = (int)(xi * T.inv_step);
   i = i > G - 2 ? G - 2 : i;
-  if (i > 0 && dq_grid_z(i, G, T.step, T.z_max) >= xi) --i;
-  if (i < G - 2 && dq_grid_z(i + 1, G, T.step, T.z_max) < xi) ++i;
-  const double x0 = dq_grid_z(i, G, T.step, T.z_max);
-  const double h_i = dq_grid_z(i + 1, G, T.step, T.z_max) - x0;
+  if (i > 0 && grid_z(i, G, T.step, T.z_max) >= xi) --i;
+  if (i < G - 2 && grid_z(i + 1, G, T.step, T.z_max) < xi) ++i;
+  const double x0 = grid_z(i, G, T.step, T.z_max);
+  const double h_i = grid_z(i + 1, G, T.step, T.z_max) - x0;
   const double t = (xi - x0) / h_i;
   const double t2 = t * t, t3 = t2 * t;
   const double h00 = 2 * t3 - 3 * t2 + 1, h10 = t3 - 2 * t2 + t, h01 = -2 * t3 + 3 * t2, h11 = t3 - t2;
   return h00 * T.at(i).y + h10 * h_i * dq_pchip_slope(T, i) + h01 * T.at(i + 1).y + h11 * h_i * dq_pchip_slope(T, i + 1);
 }
 
-// dynamic LDS: the skewed table, then DQ_TPB chunk totals and the row's r_d
-__device__ __host__ inline int dq_chunk_shift(int G) {
-  int chs = 0;
-  while ((DQ_TPB << chs) < G) ++chs;
-  return chs;
-}
-__device__ __host__ inline size_t dq_table_slots(int G, int chs) { return (size_t)G + (size_t)(G >> chs) + 1; }
+// dynamic LDS: the skewed table (cosmofit_device.h: chunk_shift<DQ_TPB>, table_slots), then DQ_TPB chunk totals and the row's r_d
 
 __global__ void __launch_bounds__(DQ_TPB)
 curves_kernel(cf_dev_desc d, const double* __restrict__ theta, int64_t S, int code, int chs, const double* __restrict__ z, int nz,
@@ -315,7 +305,7 @@ curves_kernel(cf_dev_desc d, const double* __restrict__ theta, int64_t S, int co
   if (row >= S) return;
   const int tid = threadIdx.x, G = d.n_grid;
   d2* tab = reinterpret_cast<d2*>(dq_smem);
-  double* tot = reinterpret_cast<double*>(tab + dq_table_slots(G, chs));  // [DQ_TPB] chunk totals, then r_d
+  double* tot = reinterpret_cast<double*>(tab + table_slots(G, chs));  // [DQ_TPB] chunk totals, then r_d
   const double* th = theta + row * d.ndim;
   const DqCosmo wc = dq_cosmo(d, th);
   const bool need_rd = code == CF_CURVE_DV_RD || code == CF_CURVE_DM_RD || code == CF_CURVE_DH_RD;
@@ -326,7 +316,7 @@ curves_kernel(cf_dev_desc d, const double* __restrict__ theta, int64_t S, int co
     // dh = c / H at the nodes, node g = tid, tid + 256, ... (bao/desi_cmb.py:61)
     for (int g = tid; g < G; g += DQ_TPB) {
       const double nu = d.nu_grid ? d.nu_grid[g] : -1.0;
-      tab[g + (g >> chs)].y = d.c / (wc.H0 * sqrt(dq_e2(d, wc, dq_grid_z(g, G, d.step, d.z_max), nu)));
+      tab[g + (g >> chs)].y = d.c / (wc.H0 * sqrt(dq_e2(d, wc, grid_z(g, G, d.step, d.z_max), nu)));
     }
     __syncthreads();
     // cumulative trapezoid (:62-64): thread t sums its 2^chs nodes in order, then the totals of the threads before it in order
@@ -337,7 +327,7 @@ curves_kernel(cf_dev_desc d, const double* __restrict__ theta, int64_t S, int co
     for (int k = 0; k < n_own; ++k) {
       const int g = g0 + k, p = g + (g >> chs);
       const double cur = tab[p].y;
-      if (g >= 1) run += (prev + cur) / 2 * (dq_grid_z(g, G, d.step, d.z_max) - dq_grid_z(g - 1, G, d.step, d.z_max));
+      if (g >= 1) run += (prev + cur) / 2 * (grid_z(g, G, d.step, d.z_max) - grid_z(g - 1, G, d.step, d.z_max));
       tab[p].x = run;
       prev = cur;
     }
@@ -390,12 +380,12 @@ static int cf_derived_launch(const cf_dev_desc& d, const cf_derived_kargs& a, co
 
 static int cf_curves_launch(const cf_dev_desc& d, const double* d_theta, int64_t S, int code, const double* d_z, int nz, double* d_out,
                      hipStream_t st) {
-  const int chs = dq_chunk_shift(d.n_grid);
-  const size_t lds = dq_table_slots(d.n_grid, chs) * sizeof(d2) + (DQ_TPB + 2) * sizeof(double);
+  const int chs = chunk_shift<DQ_TPB>(d.n_grid);
+  const size_t lds = table_slots(d.n_grid, chs) * sizeof(d2) + (DQ_TPB + 2) * sizeof(double);
   // 4000 nodes are 64 KB of table: at the 64 KiB a launch may take by default.  The first launch on a device raises the kernel's
   // allowance, once, to the largest table cf_create accepts (8192 nodes).
   static std::atomic<bool> raised[DQ_MAX_DEVICES];
-  const int max_lds = (int)(dq_table_slots(8192, dq_chunk_shift(8192)) * sizeof(d2) + (DQ_TPB + 2) * sizeof(double));
+  const int max_lds = (int)(table_slots(8192, chunk_shift<DQ_TPB>(8192)) * sizeof(d2) + (DQ_TPB + 2) * sizeof(double));
   if (lds > 32 * 1024) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0) return cf_set_error(CF_ERR_HIP, "cf_curves_device: hipGetDevice failed");

@@ -4,6 +4,7 @@
 #ifndef COSMOFIT_DEVICE_H
 #define COSMOFIT_DEVICE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #define CF_MAX_NDIM 16
@@ -316,5 +317,31 @@ CF_HD static inline int cf_diag_tile(int NW, int v, int j) {
   const int chunk = j >> 1, span = 2 * NW;
   return (j & 1) ? chunk * span + span - 1 - v : chunk * span + v;
 }
+
+// ---- geometry the host and the kernels must agree on --------------------------------------------------------------------------
+// The skewed LDS table of the distance-table builds: thread t of TPB owns the 2^chs consecutive nodes from t << chs, and node g
+// lives in slot g + (g >> chs), one spare 16-byte slot per chunk, so that the threads' strided walks spread over the banks.
+template <int TPB>
+CF_HD inline int chunk_shift(int n) {
+  int chs = 0;
+  while ((TPB << chs) < n) ++chs;
+  return chs;
+}
+CF_HD inline size_t table_slots(int n, int chs) { return (size_t)n + (size_t)(n >> chs) + 1; }
+
+// Dynamic LDS of walker_kernel / walker_fast_kernel / walker_stream_kernel: the skewed {cum, dh} table of the n_grid nodes (chs =
+// cf_dev_desc::chunk_shift) and one slot more.
+CF_HD inline size_t walker_lds_bytes(int n_grid, int chs) { return (table_slots(n_grid, chs) + 1) * sizeof(cf_d2); }
+
+// Dynamic LDS of growth_kernel, in doubles: {delta', d delta'/dx} at the steps + 1 boundaries, the four waves' 2 x 2 products
+// [16], the residuals and delta(a = 1) [CF_MAX_FS8 + 2], the partial column sums of the quadratic form [4][64].
+CF_HD inline size_t growth_lds_bytes(int steps) { return (size_t)(2 * (steps + 1) + 16 + CF_MAX_FS8 + 2 + 256) * sizeof(double); }
+
+#ifdef __HIPCC__
+// Grid node i of np.linspace(0, z_max, G): i*step, last node forced to z_max (sn/pantheon.py:16).
+__device__ __forceinline__ double grid_z(int i, int G, double step, double z_max) {
+  return i == G - 1 ? z_max : (double)i * step;
+}
+#endif
 
 #endif

@@ -15,7 +15,7 @@
 // 1 + w is formed directly (thawing: 2 (1 + w0) a^3 / D), never as 1 + (-1 + x), which loses x below a ~ 0.01.
 //
 // Order of the sums: thread t adds its 2^chs consecutive nodes in node order; the thread totals are scanned inside each wave by
-// the DPP scan of cf_wave_scan.h (a fixed tree over 64 lanes); the wave totals before a wave are added left to right.  chs
+// the DPP scan of cf_wave.h (a fixed tree over 64 lanes); the wave totals before a wave are added left to right.  chs
 // depends on n_a alone, so a row's bits depend neither on S, nor on its position, nor on the launch grid.  All terms are
 // positive: every prefix stays within n_a eps relative of the exact sum whatever the order.
 //
@@ -32,7 +32,8 @@
 
 #include "../../include/cosmofit.h"
 #include "cf_host.h"
-#include "cf_wave_scan.h"
+#include "cf_wave.h"
+#include "cosmofit_device.h"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
@@ -177,16 +178,10 @@ __device__ __forceinline__ double fd_phi_of_t(const FdTable& T, double x) {
   return (e1.x - e0.x) / (e1.y - e0.y) * (x - e0.y) + e0.x;
 }
 
-__device__ __host__ inline int fd_chunk_shift(int n) {
-  int chs = 0;
-  while ((FD_TPB << chs) < n) ++chs;
-  return chs;
-}
-__device__ __host__ inline size_t fd_table_slots(int n, int chs) { return (size_t)n + (size_t)(n >> chs) + 1; }
-// dynamic LDS: the skewed table, FD_TPB inclusive thread totals, then the row's parameters and flags
+// dynamic LDS: the skewed table (cosmofit_device.h: chunk_shift<FD_TPB>, table_slots), FD_TPB inclusive thread totals, then the row's parameters and flags
 #define FD_TAIL_DOUBLES 16
 __device__ __host__ inline size_t fd_lds_bytes(int n) {
-  return fd_table_slots(n, fd_chunk_shift(n)) * sizeof(d2) + (size_t)FD_TPB * sizeof(d2) + FD_TAIL_DOUBLES * sizeof(double);
+  return table_slots(n, chunk_shift<FD_TPB>(n)) * sizeof(d2) + (size_t)FD_TPB * sizeof(d2) + FD_TAIL_DOUBLES * sizeof(double);
 }
 
 // one instance per dark-energy form: the thawing one carries no exp / log and needs half the registers of the others
@@ -199,7 +194,7 @@ field_kernel(fd_desc d, const double* __restrict__ theta, int64_t S, fd_args q) 
   const int tid = threadIdx.x, n = d.n_a, chs = d.chs;
   constexpr int fde = FDE;
   d2* tab = reinterpret_cast<d2*>(fd_smem);
-  d2* tot = tab + fd_table_slots(n, chs);                  // [FD_TPB] inclusive scans of the thread totals, per wave
+  d2* tot = tab + table_slots(n, chs);                  // [FD_TPB] inclusive scans of the thread totals, per wave
   double* par = reinterpret_cast<double*>(tot + FD_TPB);   // H0 Om w0 wa, then the status of the parameters
   const double nan = __builtin_nan("");
 
@@ -426,7 +421,7 @@ int fd_validate(const char* fn, const cf_field_desc* c, int64_t S, const cf_fiel
   d.fde = c->fde;
   d.n_a = c->n_a;
   d.ndim = c->ndim;
-  d.chs = fd_chunk_shift(c->n_a);
+  d.chs = chunk_shift<FD_TPB>(c->n_a);
   d.a_min = c->a_min;
   d.a_max = c->a_max;
   d.step = (c->a_max - c->a_min) / (double)(c->n_a - 1);  // np.linspace

@@ -30,6 +30,7 @@
 
 #include "../../include/cosmofit.h"
 #include "cf_handle.h"
+#include "cf_wave.h"
 #include "cosmofit_group.h"
 #include "cosmofit_resid.h"
 
@@ -138,29 +139,6 @@ __global__ void __launch_bounds__(PG_TPB) prec_gemm_kernel(cf_infl_src src, int6
 #define IR_TPB 256
 #define IR_ROWS_PER_WG (IR_TPB / 64)
 
-__device__ __forceinline__ double infl_wave_sum(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-  return x;
-}
-
-// np.argmax's order on (value, index): a NaN beats every number, among equals the lower index wins
-__device__ __forceinline__ bool infl_before(double a, int ia, double b, int ib) {
-  const bool an = a != a, bn = b != b;
-  if (an != bn) return an;
-  if (an || a == b) return ia < ib;
-  return a > b;
-}
-
-__device__ __forceinline__ void infl_wave_argmax(double& v, int& idx) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const double vo = __shfl_xor(v, m);
-    const int io = __shfl_xor(idx, m);
-    if (infl_before(vo, io, v, idx)) { v = vo; idx = io; }
-  }
-}
-
 __global__ void __launch_bounds__(IR_TPB) infl_row_kernel(cf_infl_src src, int64_t rows, cf_infl_rows a) {
   const int lane = threadIdx.x & 63;
   const int64_t s = (int64_t)blockIdx.x * IR_ROWS_PER_WG + (threadIdx.x >> 6);
@@ -181,13 +159,13 @@ __global__ void __launch_bounds__(IR_TPB) infl_row_kernel(cf_infl_src src, int64
     if (a.contrib) a.contrib[o + i] = c;
     if (a.z) a.z[o + i] = z;
     if (a.loo) a.loo[o + i] = e;
-    if (infl_before(fabs(z), i, zmax, zidx)) { zmax = fabs(z); zidx = i; }
-    if (infl_before(drop, i, dmax, didx)) { dmax = drop; didx = i; }
+    if (argmax_before(fabs(z), i, zmax, zidx)) { zmax = fabs(z); zidx = i; }
+    if (argmax_before(drop, i, dmax, didx)) { dmax = drop; didx = i; }
   }
   if (!a.sample) return;
-  chi = infl_wave_sum(chi);
-  infl_wave_argmax(zmax, zidx);
-  infl_wave_argmax(dmax, didx);
+  chi = wave_sum(chi);
+  wave_argmax(zmax, zidx);
+  wave_argmax(dmax, didx);
   if (lane == 0) {
     double* out = a.sample + (int64_t)CF_INFL_NCOL * s;
     out[CF_IS_CHI2] = chi;

@@ -26,7 +26,7 @@
 #include <stdint.h>
 
 #include "cosmofit_device.h"
-#include "cf_wave_scan.h"
+#include "cf_wave.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -246,10 +246,7 @@ __device__ __forceinline__ double div_pos(double a, double b) {
   return fma(-fma(b, q, -a), r, q);
 }
 
-// Grid node i of np.linspace(0, z_max, G): i*step, last node forced to z_max (sn/pantheon.py:16).
-__device__ __forceinline__ double grid_z(int i, int G, double step, double z_max) {
-  return i == G - 1 ? z_max : (double)i * step;
-}
+// grid_z (node i of np.linspace(0, z_max, G)): cosmofit_device.h
 
 // the same at grid node g, with the tabulated neutrino density of that node
 template <int MODEL, int FDE>
@@ -440,7 +437,7 @@ __device__ __forceinline__ double log10_tab(double x, const d2* __restrict__ tab
   return fma_vsv(ek, log10_2hi, t.y) + fma(r, p, ek * log10_2lo);
 }
 
-// dpp_move / wave_inclusive_scan: cf_wave_scan.h
+// dpp_move / wave_inclusive_scan: cf_wave.h
 
 // Build the table.  All CF_TPB_A threads call it.
 //   dh[g]  = c/H(z_g)

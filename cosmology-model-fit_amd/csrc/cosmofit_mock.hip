@@ -25,6 +25,7 @@
 #include "../../include/cosmofit.h"
 #include "cf_handle.h"
 #include "cf_rng.h"
+#include "cf_wave.h"
 #include "cosmofit_resid.h"
 
 // Where the residual rows of a chunk lie (the accessor path's outputs in the handle's workspace, as cf_resid_src) and the
@@ -47,12 +48,6 @@ struct cf_mock_args {
 #define MK_TPB 256
 #define MK_ROWS_PER_WG (MK_TPB / 64)
 
-__device__ __forceinline__ double mock_wave_sum(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-  return x;
-}
-
 __global__ void __launch_bounds__(MK_TPB) mock_shift_kernel(cf_mock_args a, int64_t rows, const int32_t* __restrict__ mock,
                                                             double* __restrict__ out, double* __restrict__ cross) {
   const int lane = threadIdx.x & 63;
@@ -71,14 +66,14 @@ __global__ void __launch_bounds__(MK_TPB) mock_shift_kernel(cf_mock_args a, int6
       const double* __restrict__ g = a.g_sn + (int64_t)k * a.n_sn;
       double p = 0.0;
       for (int i = lane; i < a.n_sn; i += 64) p += r[i] * g[i];
-      x_sn = mock_wave_sum(p);
+      x_sn = wave_sum(p);
     }
     if (a.n_bao > 0) {
       const double* __restrict__ t = a.bao_theory + s * (int64_t)a.n_bao;
       const double* __restrict__ g = a.g_bao + (int64_t)k * a.n_bao;
       double p = 0.0;
       for (int i = lane; i < a.n_bao; i += 64) p += (a.bao_val[i] - t[i]) * g[i];
-      x_bao = mock_wave_sum(p);
+      x_bao = wave_sum(p);
     }
     if (a.n_cmb > 0) {
       double p = 0.0;
@@ -86,7 +81,7 @@ __global__ void __launch_bounds__(MK_TPB) mock_shift_kernel(cf_mock_args a, int6
         const double prior = lane == 0 ? a.cmb_prior[0] : (lane == 1 ? a.cmb_prior[1] : a.cmb_prior[2]);
         p = (prior - a.b8[8 * s + 2 + lane]) * a.g_cmb[(int64_t)k * 3 + lane];
       }
-      x_cmb = mock_wave_sum(p);
+      x_cmb = wave_sum(p);
     }
     const double shift = 2.0 * ((x_sn + x_bao) + x_cmb) + a.c[k];
     if (a.out_kind == CF_OUT_CHI2)

@@ -9,7 +9,7 @@
 //   1. each grid's cumulative table goes to LDS (G doubles: 24 KB at G = 3000, 48 KB for two grids): thread t owns a
 //      contiguous chunk of nodes, sums its intervals in order (one interval per node: width x (y_prev + y) / 2, as scipy's
 //      cumulative_trapezoid), the chunk totals are scanned with the wave64 DPP scan of the distance-table build
-//      (cf_wave_scan.h) and the four wave totals in order;
+//      (cf_wave.h) and the four wave totals in order;
 //   2. the SN residuals obs - offset - mu(z) go to Delta[w][n_ld] in the layout the solve kernels read (tri_gemm_* /
 //      trsm_chi2_kernel then compute Delta^T C^-1 Delta unchanged);
 //   3. chi2_q and sum ln(sigma^2 + s^2) over the quasars, each a per-thread sum in index order then the fixed-order block sum;
@@ -33,7 +33,7 @@
 
 #include "../../include/cosmofit.h"
 #include "cf_handle.h"
-#include "cf_wave_scan.h"
+#include "cf_wave.h"
 #include "cosmofit_device.h"
 
 #define QSR_TPB 256

@@ -27,6 +27,7 @@
 
 #include "../../include/cosmofit.h"
 #include "cf_handle.h"
+#include "cf_wave.h"
 #include "cosmofit_resid.h"
 
 #define RS_TPB 256
@@ -37,20 +38,6 @@ __device__ __forceinline__ double resid_at(const cf_resid_src& src, int64_t s, i
 }
 __device__ __forceinline__ double y_at(const cf_resid_src& src, int64_t s, int i) {
   return src.bao ? src.data[i] : src.data[i] - src.mu_corr[s * (int64_t)src.n + i];
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-  return x;
-}
-
-// np.argmax's order on (value, index): a NaN beats every number, among equals the lower index wins
-__device__ __forceinline__ bool pull_before(double a, int ia, double b, int ib) {
-  const bool an = a != a, bn = b != b;
-  if (an != bn) return an;
-  if (an || a == b) return ia < ib;
-  return a > b;
 }
 
 __global__ void __launch_bounds__(RS_TPB) resid_sample_kernel(cf_resid_src src, int64_t rows, double* __restrict__ out,
@@ -77,16 +64,18 @@ __global__ void __launch_bounds__(RS_TPB) resid_sample_kernel(cf_resid_src src, 
     sy += y_at(src, s, i);
     ss += r * r;
     const double p = fabs(r) / src.sigma[i];
-    if (pull_before(p, i, pmax, pidx)) { pmax = p; pidx = i; }
+    if (argmax_before(p, i, pmax, pidx)) { pmax = p; pidx = i; }
   }
   sr = wave_sum(sr);
   sy = wave_sum(sy);
   ss = wave_sum(ss);
+  // wave_argmax (cf_wave.h) written out: through the helper's references the compiler allocates this kernel's registers
+  // differently, and the kernel is held to its machine code
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
     const double po = __shfl_xor(pmax, m);
     const int io = __shfl_xor(pidx, m);
-    if (pull_before(po, io, pmax, pidx)) { pmax = po; pidx = io; }
+    if (argmax_before(po, io, pmax, pidx)) { pmax = po; pidx = io; }
   }
   const double inv_n = 1.0 / (double)n;
   const double rbar = sr * inv_n, ybar = sy * inv_n;

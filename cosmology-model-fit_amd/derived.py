@@ -30,6 +30,7 @@ import torch
 
 from . import _lib as L
 from . import chain_stats, marginals
+from ._args import ptr, sample_rows, single_device_engine, stream_of
 
 MAX_COLUMNS = marginals.MAX_NDIM  # marginals.corner_data takes at most this many columns
 _GL_NAMES = ("rs_star", "DM_star", "theta_star100", "R", "lA")
@@ -84,15 +85,7 @@ def _missing(info: dict, name: str, consts: dict) -> Optional[str]:
     return "to be a known quantity"
 
 
-def _check_engine(engine, what: str) -> dict:
-    info = getattr(engine, "model_info", None)
-    if info is None:
-        raise ValueError(f"{what} takes a LikelihoodEngine (or a likelihood mirror's .engine)")
-    if info["quasar"]:
-        raise ValueError(f"{what}: a quasar engine has no derived quantities or prediction curves")
-    if info["multi_device"]:
-        raise ValueError(f"{what}: the engine spans several devices; use one engine per device")
-    return info
+_QUASAR = "no derived quantities or prediction curves"
 
 
 class Spec:
@@ -104,7 +97,7 @@ class Spec:
 
     def __init__(self, engine, names: Sequence[str], *, comp: Optional[dict] = None, zdrag_fit=None, rdrag_fit=None,
                  zeq_or_h2: Optional[float] = None):
-        info = _check_engine(engine, "Spec")
+        info = single_device_engine(engine, "Spec", _QUASAR)
         if isinstance(names, str) or len(names) < 1:
             raise ValueError("Spec takes a non-empty sequence of names")
         if comp is not None:
@@ -160,9 +153,6 @@ class Spec:
         self._args = np.array([arg for _, _, arg in self._scalar], dtype=np.float64)
         self._scalar_cols = [col for col, _, _ in self._scalar]
 
-    def _p(self, a):
-        return a.ctypes.data_as(C.c_void_p)
-
     def host_columns(self, theta: np.ndarray) -> np.ndarray:
         """The same columns for host rows [n, ndim] -> [n, n_q] numpy (cf_derived / cf_curves, synchronous)."""
         th = np.ascontiguousarray(theta, dtype=np.float64)
@@ -172,28 +162,15 @@ class Spec:
         out = np.empty((n, self.n_q))
         if self._scalar:
             tmp = np.empty((n, len(self._scalar)))
-            L.check(lib.cf_derived(h, self._p(th), n, self._p(self._codes), self._p(self._args), len(self._scalar),
-                                   C.cast(C.pointer(self._consts), C.c_void_p), self._p(tmp)))
+            L.check(lib.cf_derived(h, ptr(th), n, ptr(self._codes), ptr(self._args), len(self._scalar),
+                                   C.cast(C.pointer(self._consts), C.c_void_p), ptr(tmp)))
             out[:, self._scalar_cols] = tmp
         for code, items in self._at.items():
             z = np.array([zz for _, zz in items], dtype=np.float64)
             tmp = np.empty((n, len(items)))
-            L.check(lib.cf_curves(h, self._p(th), n, code, self._p(z), len(items), self._p(tmp)))
+            L.check(lib.cf_curves(h, ptr(th), n, code, ptr(z), len(items), ptr(tmp)))
             out[:, [col for col, _ in items]] = tmp
         return out
-
-
-def _rows(samples, ndim: int, what: str) -> torch.Tensor:
-    """Shape and type first, the device last: a wrong argument is reported the same with and without a GPU."""
-    if not isinstance(samples, torch.Tensor):
-        raise ValueError(f"{what} takes a tensor on an MI355X (there is no CPU implementation to fall back to)")
-    if samples.dtype != torch.float64:
-        raise ValueError(f"{what} takes float64")
-    if samples.dim() != 2 or samples.shape[1] != ndim:
-        raise ValueError(f"{what} takes samples [n, {ndim}]")
-    if samples.shape[0] > 2**31 - 1:
-        raise ValueError(f"{what} takes at most 2^31 - 1 rows")
-    return chain_stats._on_device(samples, what).contiguous()
 
 
 def _launch_curves(engine, x: torch.Tensor, code: int, z: torch.Tensor, out: torch.Tensor, stream: int):
@@ -203,18 +180,18 @@ def _launch_curves(engine, x: torch.Tensor, code: int, z: torch.Tensor, out: tor
 def columns(spec: Spec, samples: torch.Tensor) -> torch.Tensor:
     """The quantities of `spec` for every row of samples [n, ndim]: [n, n_q] float64 on the samples' device, in the order of
     ``spec.names``.  Asynchronous on torch's current stream; nothing is copied to the host."""
-    x = _rows(samples, spec.ndim, "columns")
+    x = sample_rows(samples, spec.ndim, "columns")
     n, dev = x.shape[0], x.device
     out = torch.empty((n, spec.n_q), dtype=torch.float64, device=dev)
     if n == 0:
         return out
     lib = L.lib()
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = stream_of(dev)
         if spec._scalar:
             direct = not spec._at  # every column comes from the scalar kernel, in order
             tmp = out if direct else torch.empty((n, len(spec._scalar)), dtype=torch.float64, device=dev)
-            L.check(lib.cf_derived_device(spec.engine._h, x.data_ptr(), n, spec._p(spec._codes), spec._p(spec._args),
+            L.check(lib.cf_derived_device(spec.engine._h, x.data_ptr(), n, ptr(spec._codes), ptr(spec._args),
                                           len(spec._scalar), C.cast(C.pointer(spec._consts), C.c_void_p), tmp.data_ptr(),
                                           stream))
             if not direct:
@@ -233,7 +210,7 @@ def augment(spec: Spec, samples: torch.Tensor) -> torch.Tensor:
     if isinstance(samples, torch.Tensor) and samples.dim() == 2 and samples.shape[1] + spec.n_q > MAX_COLUMNS:
         raise ValueError(f"{samples.shape[1]} sampled + {spec.n_q} derived columns exceed the {MAX_COLUMNS} columns marginals takes; "
                          f"pass fewer names, or select columns of `columns(spec, samples)`")
-    x = _rows(samples, spec.ndim, "augment")
+    x = sample_rows(samples, spec.ndim, "augment")
     return torch.cat([x, columns(spec, x)], dim=1)
 
 
@@ -257,19 +234,19 @@ def curves(spec_or_engine, samples: torch.Tensor, z, quantity: str) -> torch.Ten
     [n, nz] float64 on the samples' device.  Each sample builds its own distance table once (the engine's n_grid nodes) and
     serves all redshifts from it; any order of z, beyond the grid by linear extrapolation as the scripts' ``DM_z``."""
     engine = spec_or_engine.engine if isinstance(spec_or_engine, Spec) else spec_or_engine
-    info = _check_engine(engine, "curves")
+    info = single_device_engine(engine, "curves", _QUASAR)
     code = _curve_code(quantity)
     miss = _missing(info, quantity, {})
     if miss:
         raise ValueError(f"{quantity} needs {miss}, which this engine lacks")
     zs = _z_array(z)
-    x = _rows(samples, info["ndim"], "curves")
+    x = sample_rows(samples, info["ndim"], "curves")
     n, dev = x.shape[0], x.device
     out = torch.empty((n, zs.size), dtype=torch.float64, device=dev)
     if n == 0:
         return out
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = stream_of(dev)
         zd = torch.from_numpy(zs).to(dev)
         if zs.size <= L.CF_CURVE_MAX_NZ:
             _launch_curves(engine, x, code, zd, out, stream)

@@ -17,6 +17,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib as L
+from ._args import ptr, stream_of
 
 C_KM_S = 299792.458  # scipy.constants.c / 1000 (sn/pantheon.py:12)
 
@@ -32,9 +33,6 @@ class Param:
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def solve_mode_of(solve="auto", latency_mode=None) -> int:
@@ -138,7 +136,7 @@ class LikelihoodEngine:
                 dev_arr = np.ascontiguousarray(list(devices), dtype=np.int32)
                 if dev_arr.size < 1:
                     raise ValueError("devices must name at least one device")
-                d.n_devices, d.devices = dev_arr.size, _ptr(dev_arr)
+                d.n_devices, d.devices = dev_arr.size, ptr(dev_arr)
         unknown = set(params) - set(L.SLOTS)
         if unknown:
             raise ValueError(f"unknown parameter slots {sorted(unknown)}; valid: {L.SLOTS}")
@@ -160,29 +158,29 @@ class LikelihoodEngine:
             keep += [z_cmb, z_hel, obs, chol, step]
             d.n_sn = z_cmb.size
             self.sn_z = z_cmb.copy()
-            d.sn_z_cmb, d.sn_z_hel, d.sn_obs, d.sn_step = _ptr(z_cmb), _ptr(z_hel), _ptr(obs), _ptr(step)
+            d.sn_z_cmb, d.sn_z_hel, d.sn_obs, d.sn_step = ptr(z_cmb), ptr(z_hel), ptr(obs), ptr(step)
             d.sn_z_turn = float(sn.get("z_turn", 0.15))
             d.sn_vel_mode = 1 if sn.get("vel_mult", False) else 0
-            d.sn_chol, d.sn_chol_ld = _ptr(chol), chol.shape[1]
+            d.sn_chol, d.sn_chol_ld = ptr(chol), chol.shape[1]
             self.mock_data["sn_chol"] = chol
             if sn.get("fixed_mu") is not None:
                 fm = _f64(sn["fixed_mu"])
                 if fm.size != z_cmb.size:
                     raise ValueError("sn['fixed_mu'] must have one entry per SN (NaN where unused)")
                 keep.append(fm)
-                d.sn_fixed_mu = _ptr(fm)
+                d.sn_fixed_mu = ptr(fm)
             if sn.get("lin_coef") is not None:
                 lc = _f64(sn["lin_coef"])
                 if lc.size != z_cmb.size:
                     raise ValueError("sn['lin_coef'] must have one entry per SN")
                 keep.append(lc)
-                d.sn_lin_coef = _ptr(lc)
+                d.sn_lin_coef = ptr(lc)
             if sn.get("dirs") is not None:
                 dirs = _f64(sn["dirs"])
                 if dirs.shape != (z_cmb.size, 3):
                     raise ValueError("sn['dirs'] must be (N, 3)")
                 keep.append(dirs)
-                d.sn_dir = _ptr(dirs)
+                d.sn_dir = ptr(dirs)
         self.n_bao = 0
         if physical is not None:
             d.or_h2, d.omnu_h2, d.o_gamma_h2 = physical["or_h2"], physical["omnu_h2"], physical["o_gamma_h2"]
@@ -195,7 +193,7 @@ class LikelihoodEngine:
             if not (bz.size == bv.size == bq.size) or binv.shape != (bz.size, bz.size):
                 raise ValueError("bao: z, val, qty must have n entries and inv_cov must be (n, n)")
             keep += [bz, bv, binv, bq]
-            d.n_bao, d.bao_z, d.bao_val, d.bao_qty, d.bao_inv_cov = bz.size, _ptr(bz), _ptr(bv), _ptr(bq), _ptr(binv)
+            d.n_bao, d.bao_z, d.bao_val, d.bao_qty, d.bao_inv_cov = bz.size, ptr(bz), ptr(bv), ptr(bq), ptr(binv)
             d.bao_dh_mode = 1 if bao.get("dh_exact", False) else 0
             if bao.get("rd_fit") is not None:
                 d.rd_mode = 1
@@ -210,7 +208,7 @@ class LikelihoodEngine:
             if cz.size != ch.size or cinv.shape != (cz.size, cz.size):
                 raise ValueError("cc: z, h must have n entries and inv_cov must be (n, n)")
             keep += [cz, ch, cinv]
-            d.n_cc, d.cc_z, d.cc_h, d.cc_inv_cov, d.cc_logdet = cz.size, _ptr(cz), _ptr(ch), _ptr(cinv), float(cc["logdet"])
+            d.n_cc, d.cc_z, d.cc_h, d.cc_inv_cov, d.cc_logdet = cz.size, ptr(cz), ptr(ch), ptr(cinv), float(cc["logdet"])
             d.cc_f_mode = 1 if cc.get("f_inverse", False) else 0
         self.n_fs8 = 0
         if fs8 is not None:
@@ -219,7 +217,7 @@ class LikelihoodEngine:
             if not (fz.size == fv.size == ffid.size) or finv.shape != (fz.size, fz.size):
                 raise ValueError("fs8: z, val, fid must have n entries and inv_cov must be (n, n)")
             keep += [fz, fv, finv, ffid]
-            d.n_fs8, d.fs8_z, d.fs8_val, d.fs8_inv_cov, d.fs8_fid = fz.size, _ptr(fz), _ptr(fv), _ptr(finv), _ptr(ffid)
+            d.n_fs8, d.fs8_z, d.fs8_val, d.fs8_inv_cov, d.fs8_fid = fz.size, ptr(fz), ptr(fv), ptr(finv), ptr(ffid)
             d.fs8_a_init, d.fs8_steps = float(fs8["a_init"]), int(fs8.get("steps", 0))
             d.fs8_n_agrid = int(fs8.get("a_grid", 0))
             self.n_fs8 = int(fz.size)
@@ -228,7 +226,7 @@ class LikelihoodEngine:
             gx, gw = np.polynomial.legendre.leggauss(int(cmb.get("n_gl", 100)))  # cmb/data_planck_act_compression.py:150
             gx, gw = _f64(gx), _f64(gw)
             keep += [gx, gw]
-            d.cmb_mode, d.n_gl, d.gl_x, d.gl_w = int(cmb["mode"]), gx.size, _ptr(gx), _ptr(gw)
+            d.cmb_mode, d.n_gl, d.gl_x, d.gl_w = int(cmb["mode"]), gx.size, ptr(gx), ptr(gw)
             d.cmb_prior[:] = [float(x) for x in cmb["prior"]]
             d.cmb_inv_cov[:] = [float(x) for x in np.asarray(cmb["inv_cov"], dtype=np.float64).ravel()]
             d.zstar_fit[:] = [float(x) for x in tuple(cmb["zstar_fit"]) + ZSTAR_CONSTS]
@@ -236,7 +234,7 @@ class LikelihoodEngine:
             self.mock_data["cmb_prior"] = np.asarray(cmb["prior"], dtype=np.float64).reshape(3).copy()
             self.mock_data["cmb_mode"] = int(cmb["mode"])
         self.bounds = None if bounds is None else _f64(bounds).reshape(ndim, 2)
-        d.bounds = _ptr(self.bounds)
+        d.bounds = ptr(self.bounds)
         g = (L.cf_gauss_prior * max(len(gauss), 1))()
         for k, (idx, mean, sigma) in enumerate(gauss):
             g[k].idx, g[k].mean, g[k].sigma = int(idx), float(mean), float(sigma)
@@ -265,7 +263,7 @@ class LikelihoodEngine:
             if not (qz.size == qmu.size == qsig.size):
                 raise ValueError("quasar: z, mu, sigma must have the same length")
             keep += [qz, qmu, qsig]
-            e.n_qsr, e.qsr_z, e.qsr_mu, e.qsr_sigma = qz.size, _ptr(qz), _ptr(qmu), _ptr(qsig)
+            e.n_qsr, e.qsr_z, e.qsr_mu, e.qsr_sigma = qz.size, ptr(qz), ptr(qmu), ptr(qsig)
             for name in ("offset", "scatter"):
                 p, slot = quasar[name], getattr(e, "qsr_" + name)
                 slot.idx, slot.scale, slot.fixed = p.idx, p.scale, p.fixed
@@ -278,7 +276,7 @@ class LikelihoodEngine:
                 bq = np.ascontiguousarray(qb["qty"], dtype=np.int32)
                 keep += [bz, bv, binv, bq]
                 e.bao_mode, e.n_bao = L.CF_QSR_BAO_QUAD, bz.size
-                e.bao_z, e.bao_val, e.bao_qty, e.bao_inv_cov = _ptr(bz), _ptr(bv), _ptr(bq), _ptr(binv)
+                e.bao_z, e.bao_val, e.bao_qty, e.bao_inv_cov = ptr(bz), ptr(bv), ptr(bq), ptr(binv)
                 self.n_bao = int(bz.size)
             self.n_qsr = int(qz.size)
             L.check(lib.cf_create_quasar(C.byref(d), C.byref(e), C.byref(self._h)))
@@ -367,7 +365,7 @@ class LikelihoodEngine:
             out = torch.empty(theta.shape[0], dtype=torch.float64, device=theta.device)
             if theta.shape[0]:
                 self.eval_device(theta.data_ptr(), theta.shape[0], out.data_ptr(), kind,
-                                 torch.cuda.current_stream(theta.device).cuda_stream)
+                                 stream_of(theta.device))
             return out
 
         f.engine = self  # what ShardedEnsemble.fit_report / DeviceNestedSampler.fit_report evaluate the residuals with
@@ -385,7 +383,7 @@ class LikelihoodEngine:
         bt = np.empty((W, nb)) if nb else None
         ft = np.empty((W, nf)) if nf else None
         blocks = np.empty((W, 10))
-        L.check(L.lib().cf_eval_parts(self._h, _ptr(th), W, _ptr(dm), _ptr(mc), _ptr(dl), _ptr(blocks), _ptr(bt), _ptr(ft)))
+        L.check(L.lib().cf_eval_parts(self._h, ptr(th), W, ptr(dm), ptr(mc), ptr(dl), ptr(blocks), ptr(bt), ptr(ft)))
         return dict(dm=dm, mu_corr=mc, delta=dl, chi2_blocks=blocks[:, :3], cmb_vector=blocks[:, 3:6], chi2_cc=blocks[:, 6],
                     chi2_fs8=blocks[:, 7], z_star=blocks[:, 8], r_drag=blocks[:, 9], bao_theory=bt, fs8_theory=ft)
 
@@ -398,7 +396,7 @@ class LikelihoodEngine:
         ms = np.empty((W, self.n_sn)) if self.n_sn else None
         mq = np.empty((W, self.n_qsr))
         bt = np.empty((W, self.n_bao)) if self.n_bao else None
-        L.check(L.lib().cf_qsr_eval_parts(self._h, _ptr(th), W, _ptr(blocks), _ptr(ms), _ptr(mq), _ptr(bt)))
+        L.check(L.lib().cf_qsr_eval_parts(self._h, ptr(th), W, ptr(blocks), ptr(ms), ptr(mq), ptr(bt)))
         return dict(chi2_blocks=blocks, mu_sn=ms, mu_qsr=mq, bao_theory=bt)
 
     def distance_table(self, theta):
@@ -407,7 +405,7 @@ class LikelihoodEngine:
         th = np.atleast_2d(_f64(theta))
         W, G = th.shape[0], self.n_grid
         cum, dh = np.empty((W, G)), np.empty((W, G))
-        L.check(L.lib().cf_eval_table(self._h, _ptr(th), W, _ptr(cum), _ptr(dh)))
+        L.check(L.lib().cf_eval_table(self._h, ptr(th), W, ptr(cum), ptr(dh)))
         return np.linspace(0, self.z_max, num=G), cum, dh
 
     def DM_z(self, theta, z):
@@ -427,7 +425,7 @@ class LikelihoodEngine:
         z = np.atleast_1d(_f64(z))
         q = np.ascontiguousarray(np.broadcast_to(np.asarray(qty), z.shape), dtype=np.int32)
         out = np.empty(z.size)
-        L.check(L.lib().cf_eval_bao_at(self._h, _ptr(th), _ptr(z), _ptr(q), z.size, _ptr(out)))
+        L.check(L.lib().cf_eval_bao_at(self._h, ptr(th), ptr(z), ptr(q), z.size, ptr(out)))
         return out
 
     def H_z(self, theta, z):
@@ -437,7 +435,7 @@ class LikelihoodEngine:
             raise ValueError(f"theta must have {self.ndim} entries")
         z = np.atleast_1d(_f64(z))
         out = np.empty(z.size)
-        L.check(L.lib().cf_eval_hz(self._h, _ptr(th), _ptr(z), z.size, _ptr(out)))
+        L.check(L.lib().cf_eval_hz(self._h, ptr(th), ptr(z), z.size, ptr(out)))
         return out
 
     def fs8_theory_at(self, theta, z):
@@ -448,7 +446,7 @@ class LikelihoodEngine:
             raise ValueError(f"theta must have {self.ndim} entries")
         z = np.atleast_1d(_f64(z))
         out = np.empty(z.size)
-        L.check(L.lib().cf_eval_fs8_at(self._h, _ptr(th), _ptr(z), z.size, _ptr(out)))
+        L.check(L.lib().cf_eval_fs8_at(self._h, ptr(th), ptr(z), z.size, ptr(out)))
         return out
 
     def derived(self, theta, names, **consts):
@@ -466,7 +464,7 @@ class LikelihoodEngine:
         if block not in L.RESID_BLOCKS:
             raise ValueError(f"block must be one of {sorted(L.RESID_BLOCKS)}")
         out = np.empty(self.n_sn if block == "sn" else self.n_bao)
-        L.check(L.lib().cf_resid_sigma(self._h, L.RESID_BLOCKS[block], _ptr(out)))
+        L.check(L.lib().cf_resid_sigma(self._h, L.RESID_BLOCKS[block], ptr(out)))
         return out
 
     def walker_form(self, W: int) -> int:
@@ -519,7 +517,7 @@ class LikelihoodEngine:
         n_ld = (self.n_sn + 63) // 64 * 64
         out = np.empty(((int(W) + 15) // 16 * 16, max(n_ld, 1)))
         layout = C.c_int32(-1)
-        L.check(L.lib().cf_last_residuals(self._h, int(W), _ptr(out), C.byref(layout)))
+        L.check(L.lib().cf_last_residuals(self._h, int(W), ptr(out), C.byref(layout)))
         return out, int(layout.value)
 
     def enable_timing(self, slots=1, stride=1):

@@ -43,6 +43,8 @@ from typing import Callable, Tuple
 
 import torch
 
+from ._args import stream_of
+
 try:
     import torch.distributed as dist
 except Exception:  # pragma: no cover
@@ -150,7 +152,7 @@ class NativeMoves:
         accepts (cf_ens_accept_record, same launch)."""
         L, lib = self.L, self.lib
         kind = _KIND[move]
-        stream = torch.cuda.current_stream(e.x.device).cuda_stream
+        stream = stream_of(e.x.device)
         # this step's active set: the shard's walkers of split `split` -- one small launch, no host sync (the count is
         # arithmetic on the shard bounds and two group permutations)
         n = active_count(split_key, n_splits, split, e.start, e.stop)
@@ -178,7 +180,102 @@ class NativeMoves:
         e._n_proposed += n
 
 
-class ShardedEnsemble:
+class ChainRecorder:
+    """What the device-resident samplers (``ShardedEnsemble``, ``replicas.ReplicaEnsemble``) share: the configured moves and the
+    per-step draw among them, and emcee's ``run_mcmc`` with its chain recorded on the device.  A sampler sets ``seed``,
+    ``step_count``, ``x``, ``logp`` and ``impl``, names the class of its library moves in ``_native`` and supplies ``step`` and
+    ``_step(record)``; record is None, or the device addresses (chain slot or None, log-P slot or None, accept counts) the
+    library's accept kernel writes the walkers' end-of-step rows and counts their accepts into."""
+    _native: type = None
+
+    def _set_moves(self, moves, de_splits: int):
+        names = set(_KIND)
+        if not moves or any(m not in names or w <= 0 for m, w in moves):
+            raise ValueError(f"moves must be a non-empty sequence of (name in {sorted(names)}, weight > 0)")
+        if de_splits not in (2, 3):
+            raise ValueError("de_splits must be 3 (emcee's DEMove) or 2")
+        tot = float(sum(w for _, w in moves))
+        self.moves = [(m, w / tot) for m, w in moves]
+        self.de_splits = de_splits
+
+    def _new_record(self, walkers: tuple, logp_dtype):
+        """Empty buffers of the recorded chain, [capacity, *walkers, ndim] / [capacity, *walkers], and the accept counts."""
+        dev = self.x.device
+        self._chain = torch.empty((0,) + walkers + (self.ndim,), dtype=self.x.dtype, device=dev)
+        self._chain_logp = torch.empty((0,) + walkers, dtype=logp_dtype, device=dev)
+        self._walker_acc = torch.zeros(math.prod(walkers), dtype=torch.int64, device=dev)
+        self._iteration, self._mcmc_steps = 0, 0
+
+    def _splits_of(self, move: str) -> int:
+        return self.de_splits if move == "de" else 2
+
+    def _pick_move(self) -> str:
+        u = uniform01_scalar(stream_key(self.seed, self.step_count, 0, _MOVE_STREAM), 0)
+        acc = 0.0
+        for name, w in self.moves:
+            acc += w
+            if u < acc:
+                return name
+        return self.moves[-1][0]
+
+    def run(self, n_steps: int):
+        for _ in range(n_steps):
+            self.step()
+        return self
+
+    def run_mcmc(self, nsteps: int, thin_by: int = 1):
+        """emcee's ``run_mcmc``: make nsteps * thin_by steps and store every thin_by-th end-of-step state (positions and
+        log P of this sampler's walkers) on the device.  With the library's kernels the accept kernel writes the slot and the
+        per-walker accept counts (cf_ens_accept_record / cf_rep_accept_record): no extra launch and no host sync per step.  Any
+        other ``moves_impl`` (the tensor statement in tests) gets the slot filled by a copy of x / log P after the step."""
+        nsteps, thin_by = int(nsteps), int(thin_by)
+        if nsteps < 0 or thin_by < 1:
+            raise ValueError("run_mcmc needs nsteps >= 0 and thin_by >= 1")
+        need = self._iteration + nsteps
+        if need > self._chain.shape[0]:  # grow once per call
+            chain = torch.empty((need,) + tuple(self._chain.shape[1:]), dtype=self._chain.dtype, device=self._chain.device)
+            logp = torch.empty((need,) + tuple(self._chain_logp.shape[1:]), dtype=self._chain_logp.dtype, device=self._chain.device)
+            chain[: self._iteration] = self._chain[: self._iteration]
+            logp[: self._iteration] = self._chain_logp[: self._iteration]
+            self._chain, self._chain_logp = chain, logp
+        native = isinstance(self.impl, self._native)
+        # slot addresses by arithmetic on the base pointers (no tensor views in the step loop)
+        chain_ptr, logp_ptr, acc_ptr = self._chain.data_ptr(), self._chain_logp.data_ptr(), self._walker_acc.data_ptr()
+        chain_row = self._chain.stride(0) * self._chain.element_size()
+        logp_row = self._chain_logp.stride(0) * self._chain_logp.element_size()
+        for i in range(nsteps * thin_by):
+            store = (i + 1) % thin_by == 0
+            slot = self._iteration
+            if native:
+                self._step((chain_ptr + slot * chain_row, logp_ptr + slot * logp_row, acc_ptr) if store else
+                           (None, None, acc_ptr))
+            else:
+                self._step(None)
+                if store:
+                    self._chain[slot].copy_(self.x)
+                    self._chain_logp[slot].copy_(self.logp.reshape(self._chain_logp.shape[1:]))
+            self._mcmc_steps += 1
+            if store:
+                self._iteration += 1
+        return self
+
+    @property
+    def iteration(self) -> int:
+        """Number of stored states (emcee's ``sampler.iteration`` at thin_by = 1)."""
+        return self._iteration
+
+    def _stored_steps(self, v: torch.Tensor, discard: int, thin: int) -> torch.Tensor:
+        """emcee's slicing of a stored quantity: the states [discard + thin - 1 :: thin] of those stored so far."""
+        if self._iteration == 0:
+            raise AttributeError("you must run the sampler with run_mcmc before accessing the results")
+        if discard < 0 or thin < 1:
+            raise ValueError("get_chain needs discard >= 0 and thin >= 1")
+        return v[discard + thin - 1: self._iteration: thin]
+
+
+class ShardedEnsemble(ChainRecorder):
+    _native = NativeMoves
+
     def __init__(self, log_prob_fn: Callable[[torch.Tensor], torch.Tensor], positions: torch.Tensor, *,
                  seed: int = 42, a: float = 2.0, moves=STRETCH_ONLY, de_sigma: float = 1e-5, group=None,
                  randomize_split: bool = True, de_splits: int = 3, moves_impl=None, blobs=None):
@@ -189,14 +286,8 @@ class ShardedEnsemble:
         moves_impl: None = the library's kernels (positions must live on a GPU); tests pass the tensor statement.
         blobs: a ``derived.Spec`` of the likelihood's engine: what ``get_blobs`` returns for the stored chain (emcee's blobs,
             cmb/cmb.py:45-63,105)."""
-        names = set(_KIND)
-        if not moves or any(m not in names or w <= 0 for m, w in moves):
-            raise ValueError(f"moves must be a non-empty sequence of (name in {sorted(names)}, weight > 0)")
-        if de_splits not in (2, 3):
-            raise ValueError("de_splits must be 3 (emcee's DEMove) or 2")
-        tot = float(sum(w for _, w in moves))
-        self.moves = [(m, w / tot) for m, w in moves]
-        self.de_sigma, self.de_splits = de_sigma, de_splits
+        self._set_moves(moves, de_splits)
+        self.de_sigma = de_sigma
         self.group = group
         self.distributed = dist is not None and dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(group) if self.distributed else 1
@@ -226,12 +317,7 @@ class ShardedEnsemble:
         # a backend without device collectives (gloo: rank processes sharing one GPU, CPU rehearsals): the all-gather of
         # device-resident positions is staged through the host
         self._host_staged = self.distributed and self.x.is_cuda and "nccl" not in str(dist.get_backend(group)).lower()
-        # the recorded chain (run_mcmc): this rank's walkers only, [capacity, W_local, ndim] / [capacity, W_local]
-        self._chain = torch.empty((0, self.stop - self.start, self.ndim), dtype=self.x.dtype, device=self.x.device)
-        self._chain_logp = torch.empty((0, self.stop - self.start), dtype=self.logp.dtype, device=self.x.device)
-        self._iteration = 0
-        self._walker_acc = torch.zeros(self.stop - self.start, dtype=torch.int64, device=self.x.device)
-        self._mcmc_steps = 0
+        self._new_record((self.stop - self.start,), self.logp.dtype)  # the recorded chain (run_mcmc): this rank's walkers only
         self._blobs = blobs
         if moves_impl is None:
             if not self.x.is_cuda:
@@ -272,15 +358,6 @@ class ShardedEnsemble:
             return self._all_gather(self._allpos, self.x)
         return self._gather_rows(self.x)
 
-    def _pick_move(self) -> str:
-        u = uniform01_scalar(stream_key(self.seed, self.step_count, 0, _MOVE_STREAM), 0)
-        acc = 0.0
-        for name, w in self.moves:
-            acc += w
-            if u < acc:
-                return name
-        return self.moves[-1][0]
-
     # ---- one ensemble step = the split updates of the step's move (two halves; three thirds for DE) -------------------
     def step(self):
         """Per split: all-gather -> [KDE fit] -> propose -> log P -> accept; with the library's kernels everything is
@@ -289,7 +366,7 @@ class ShardedEnsemble:
 
     def _step(self, record):
         move = self._pick_move()
-        n_splits = self.de_splits if move == "de" else 2
+        n_splits = self._splits_of(move)
         split_key = stream_key(self.seed, self.step_count, 0, _SPLIT_STREAM) if self.randomize_split else 0
         for split in range(n_splits):
             if record is None:
@@ -307,11 +384,6 @@ class ShardedEnsemble:
     def n_proposed(self) -> int:
         return self._n_proposed
 
-    def run(self, n_steps: int):
-        for _ in range(n_steps):
-            self.step()
-        return self
-
     def acceptance_fraction(self) -> float:
         acc = torch.tensor([self.n_accepted, self.n_proposed], dtype=torch.float64,
                            device="cpu" if self._host_staged else self.x.device)
@@ -320,54 +392,9 @@ class ShardedEnsemble:
         return float(acc[0] / torch.clamp(acc[1], min=1.0))
 
     # ---- emcee's results interface: a chain recorded on the device -----------------------------------------------
-    def run_mcmc(self, nsteps: int, thin_by: int = 1):
-        """emcee's ``run_mcmc``: make nsteps * thin_by steps and store every thin_by-th end-of-step state (positions and
-        log P of this rank's walkers) on the device.  With the library's kernels the accept kernel writes the slot and the
-        per-walker accept counts (cf_ens_accept_record): no extra launch and no host sync per step.  Any other
-        ``moves_impl`` (the tensor statement in tests) gets the slot filled by a copy of x / log P after the step."""
-        nsteps, thin_by = int(nsteps), int(thin_by)
-        if nsteps < 0 or thin_by < 1:
-            raise ValueError("run_mcmc needs nsteps >= 0 and thin_by >= 1")
-        need = self._iteration + nsteps
-        if need > self._chain.shape[0]:  # grow once per call
-            chain = torch.empty((need,) + tuple(self._chain.shape[1:]), dtype=self._chain.dtype, device=self._chain.device)
-            logp = torch.empty((need,) + tuple(self._chain_logp.shape[1:]), dtype=self._chain_logp.dtype, device=self._chain.device)
-            chain[: self._iteration] = self._chain[: self._iteration]
-            logp[: self._iteration] = self._chain_logp[: self._iteration]
-            self._chain, self._chain_logp = chain, logp
-        native = isinstance(self.impl, NativeMoves)
-        # slot addresses by arithmetic on the base pointers (no tensor views in the step loop)
-        chain_ptr, logp_ptr, acc_ptr = self._chain.data_ptr(), self._chain_logp.data_ptr(), self._walker_acc.data_ptr()
-        chain_row = self._chain.stride(0) * self._chain.element_size()
-        logp_row = self._chain_logp.stride(0) * self._chain_logp.element_size()
-        for i in range(nsteps * thin_by):
-            store = (i + 1) % thin_by == 0
-            slot = self._iteration
-            if native:
-                self._step((chain_ptr + slot * chain_row, logp_ptr + slot * logp_row, acc_ptr) if store else
-                           (None, None, acc_ptr))
-            else:
-                self._step(None)
-                if store:
-                    self._chain[slot].copy_(self.x)
-                    self._chain_logp[slot].copy_(self.logp)
-            self._mcmc_steps += 1
-            if store:
-                self._iteration += 1
-        return self
-
-    @property
-    def iteration(self) -> int:
-        """Number of stored states (emcee's ``sampler.iteration`` at thin_by = 1)."""
-        return self._iteration
-
     def _stored(self, local: torch.Tensor, discard: int, thin: int, flat: bool) -> torch.Tensor:
         """emcee's slicing of a stored quantity, gathered over the ranks: [n, W_total, ...] (flat: [n * W_total, ...])."""
-        if self._iteration == 0:
-            raise AttributeError("you must run the sampler with run_mcmc before accessing the results")
-        if discard < 0 or thin < 1:
-            raise ValueError("get_chain needs discard >= 0 and thin >= 1")
-        v = local[discard + thin - 1: self._iteration: thin]
+        v = self._stored_steps(local, discard, thin)
         if self.world > 1:  # walker-major for the row gather (one collective), then back to step-major
             v = self._gather_rows(v.transpose(0, 1).contiguous()).transpose(0, 1)
         v = v.contiguous()

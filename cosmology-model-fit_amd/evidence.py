@@ -29,7 +29,6 @@ There is no tensor fallback: without the HIP library or a GPU ``bridge`` raises,
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import warnings
 from dataclasses import dataclass
@@ -38,6 +37,7 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _args
 from .ensemble import _U64, _mix_int
 
 _BRIDGE_TAG = 0x4252494447455331  # "BRIDGES1": the domain tag of the proposal draws (the optimizer's is "OPTIMIZ1")
@@ -161,13 +161,8 @@ def _validate(log_prob, samples, lo, hi, log_probs, method, n_draws, n_eff, seed
     return lo, hi, d, x, lead, n_fit, n1, n2, n_eff, seed, float(tol), max_iter, chunk
 
 
-def _require_gpu():
-    from . import _lib as L
-
-    lib = L.lib()  # raises if the HIP library is missing
-    if lib.cf_device_count() < 1 or not torch.cuda.is_available():
-        raise L.CosmofitError(-2, "evidence.bridge runs in the library's HIP kernels: no GPU is visible (there is no tensor fallback)")
-    return L, lib
+def _require_gpu():  # a module attribute: a test answers for the device through it
+    return _args.require_gpu("evidence.bridge")
 
 
 def _cholesky(cov: np.ndarray) -> np.ndarray:
@@ -187,25 +182,18 @@ def _cholesky(cov: np.ndarray) -> np.ndarray:
 
 
 # ---- the device pieces ------------------------------------------------------------------------------------------------------
-def _dp(a: np.ndarray):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 class _Device:
     def __init__(self, L, lib, device, lo, hi):
         self.L, self.lib, self.device, self.lo, self.hi, self.d = L, lib, device, lo, hi, lo.size
         self.torch = torch
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
 
     def forward(self, theta, mean, chol):
         t = self.torch
         n = theta.shape[0]
         z = t.empty((n, self.d), dtype=t.float64, device=self.device)
         lj = t.empty(n, dtype=t.float64, device=self.device)
-        self.L.check(self.lib.cf_bridge_forward(theta.data_ptr(), n, self.d, _dp(self.lo), _dp(self.hi), _dp(mean), _dp(chol),
-                                                z.data_ptr(), lj.data_ptr(), self._stream()))
+        self.L.check(self.lib.cf_bridge_forward(theta.data_ptr(), n, self.d, _args.ptr(self.lo), _args.ptr(self.hi), _args.ptr(mean), _args.ptr(chol),
+                                                z.data_ptr(), lj.data_ptr(), _args.stream_of(self.device)))
         return z, lj
 
     def points(self, z, mean, chol, mirror: int):
@@ -213,14 +201,14 @@ class _Device:
         n = z.shape[0]
         theta = t.empty((n, self.d), dtype=t.float64, device=self.device)
         lj = t.empty(n, dtype=t.float64, device=self.device)
-        self.L.check(self.lib.cf_bridge_points(z.data_ptr(), n, self.d, _dp(self.lo), _dp(self.hi), _dp(mean), _dp(chol), int(mirror),
-                                               theta.data_ptr(), lj.data_ptr(), self._stream()))
+        self.L.check(self.lib.cf_bridge_points(z.data_ptr(), n, self.d, _args.ptr(self.lo), _args.ptr(self.hi), _args.ptr(mean), _args.ptr(chol), int(mirror),
+                                               theta.data_ptr(), lj.data_ptr(), _args.stream_of(self.device)))
         return theta, lj
 
     def draw(self, key: int, first: int, n: int):
         t = self.torch
         z = t.empty((n, self.d), dtype=t.float64, device=self.device)
-        self.L.check(self.lib.cf_bridge_draw(key, first, n, self.d, z.data_ptr(), self._stream()))
+        self.L.check(self.lib.cf_bridge_draw(key, first, n, self.d, z.data_ptr(), _args.stream_of(self.device)))
         return z
 
     def solve(self, l1, l2, lstar, s1, s2, tol, max_iter):
@@ -228,7 +216,7 @@ class _Device:
         rec = t.empty(self.L.CF_BRIDGE_RESULT_DOUBLES, dtype=t.float64, device=self.device)
         f2 = t.empty(l1.shape[0], dtype=t.float64, device=self.device)
         self.L.check(self.lib.cf_bridge_solve(l1.data_ptr(), l1.shape[0], l2.data_ptr(), l2.shape[0], lstar, s1, s2, tol, max_iter,
-                                              rec.data_ptr(), f2.data_ptr(), self._stream()))
+                                              rec.data_ptr(), f2.data_ptr(), _args.stream_of(self.device)))
         return dict(zip(self.L.BRIDGE_RESULT, rec.cpu().tolist())), f2  # the one host read of the solve
 
 

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import chain_stats, marginals
+from . import _args, chain_stats, marginals
 
 COLUMNS = L.RESID_COLUMNS
 BLOCK_COLUMNS = L.CHI2_BLOCK_COLUMNS
@@ -42,13 +42,7 @@ _weighted_quantile = marginals._weighted_quantile
 
 def _check_engine(engine, block: str, what: str) -> int:
     """The rules of cf_resid_device on the engine's facts, before any device work; returns the number of data of the block."""
-    info = getattr(engine, "model_info", None)
-    if info is None:
-        raise ValueError(f"{what} takes a LikelihoodEngine (or a likelihood mirror's .engine)")
-    if info["quasar"]:
-        raise ValueError(f"{what}: a quasar engine has no accessor path to take the residuals from")
-    if info["multi_device"]:
-        raise ValueError(f"{what}: the engine spans several devices; use one engine per device")
+    _args.single_device_engine(engine, what)
     if block not in L.RESID_BLOCKS:
         raise ValueError(f"block must be one of {sorted(L.RESID_BLOCKS)} (the cosmic-chronometer and growth-rate blocks export no "
                          f"theory vector)")
@@ -58,19 +52,6 @@ def _check_engine(engine, block: str, what: str) -> int:
     return n
 
 
-def _rows(samples, ndim: int, what: str) -> torch.Tensor:
-    """Shape and type first, the device last: a wrong argument is reported the same with and without a GPU."""
-    if not isinstance(samples, torch.Tensor):
-        raise ValueError(f"{what} takes a tensor on an MI355X (there is no CPU implementation to fall back to)")
-    if samples.dtype != torch.float64:
-        raise ValueError(f"{what} takes float64")
-    if samples.dim() != 2 or samples.shape[1] != ndim:
-        raise ValueError(f"{what} takes samples [n, {ndim}]")
-    if samples.shape[0] > 2**31 - 1:
-        raise ValueError(f"{what} takes at most 2^31 - 1 rows")
-    return chain_stats._on_device(samples, what).contiguous()
-
-
 def _thresholds(thresholds) -> np.ndarray:
     t = np.atleast_1d(np.asarray(thresholds, dtype=np.float64)) if thresholds is not None and len(thresholds) else np.empty(0)
     if t.ndim != 1 or t.size > L.CF_RESID_MAX_THR:
@@ -78,22 +59,6 @@ def _thresholds(thresholds) -> np.ndarray:
     if not (np.isfinite(t).all() and (t >= 0).all()):
         raise ValueError("thresholds must be finite and >= 0")
     return np.ascontiguousarray(t)
-
-
-def _row_weights(weights, x: torch.Tensor, what: str) -> Optional[torch.Tensor]:
-    """One weight per row, finite and >= 0, on the samples' device (a row of weight 0 is skipped and counted)."""
-    if weights is None:
-        return None
-    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64:
-        raise ValueError(f"{what} takes the weights as a float64 tensor")
-    if weights.dim() != 1 or weights.shape[0] != x.shape[0]:
-        raise ValueError("weights must be [n], one per sample")
-    if weights.device != x.device:
-        raise ValueError("weights must be on the device of the samples")
-    w = weights.contiguous()
-    if w.shape[0] and not bool((torch.isfinite(w) & (w >= 0)).all()):
-        raise ValueError("weights must be finite and >= 0")
-    return w
 
 
 def dof(n_data: int, ndim: int) -> int:
@@ -107,39 +72,52 @@ def set_library_chunk(engine, rows: int = 0):
     L.check(L.lib().cf_resid_set_chunk(engine._h, int(rows)))
 
 
-class Accumulator:
-    """The running per-datum state of ``cf_resid_acc`` on a device: feed it consecutive pieces of a chain with ``update`` (the
-    result is the same bits for every cut), read it with ``result``."""
+class DatumAcc:
+    """The arrays of one ``cf_resid_acc`` on a device, and the struct that points at them (``c``)."""
+
+    def __init__(self, n: int, n_thr: int, device):
+        f64 = dict(dtype=torch.float64, device=device)
+        self.w_sum, self.mean, self.m2 = (torch.zeros(n, **f64) for _ in range(3))
+        self.exceed = torch.zeros((n_thr, n), **f64)
+        self.n_used, self.n_skipped = (torch.zeros(n, dtype=torch.int64, device=device) for _ in range(2))
+        a = L.cf_resid_acc()
+        a.struct_size, a.n, a.n_thr = C.sizeof(L.cf_resid_acc), n, n_thr
+        a.w_sum, a.mean, a.m2 = self.w_sum.data_ptr(), self.mean.data_ptr(), self.m2.data_ptr()
+        a.exceed = self.exceed.data_ptr() if n_thr else None
+        a.n_used, a.n_skipped = self.n_used.data_ptr(), self.n_skipped.data_ptr()
+        self.c = a
+
+    def mean_std(self):
+        """(mean, std with ddof 0) as numpy; a datum no row was used for gives NaN."""
+        w_sum = self.w_sum.cpu().numpy()
+        mean = np.where(w_sum > 0, self.mean.cpu().numpy(), np.nan)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return mean, np.sqrt(self.m2.cpu().numpy() / w_sum)
+
+
+class Accumulator(DatumAcc):
+    """The running per-datum state of ``cf_resid_acc`` on a device (a ``DatumAcc``: the arrays are its own ``w_sum``, ``mean``,
+    ...): feed it consecutive pieces of a chain with ``update`` (the result is the same bits for every cut), read it with
+    ``result``."""
 
     def __init__(self, engine, block: str = "sn", thresholds: Sequence[float] = (2.0, 3.0), device=None):
         self.n = _check_engine(engine, block, "Accumulator")
         self.engine, self.block, self.thresholds = engine, block, _thresholds(thresholds)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        k = self.thresholds.size
-        self.w_sum, self.mean, self.m2 = (torch.zeros(self.n, **f64) for _ in range(3))
-        self.exceed = torch.zeros((k, self.n), **f64)
-        self.n_used, self.n_skipped = (torch.zeros(self.n, dtype=torch.int64, device=self.device) for _ in range(2))
-        a = L.cf_resid_acc()
-        a.struct_size, a.n, a.n_thr = C.sizeof(L.cf_resid_acc), self.n, k
-        a.w_sum, a.mean, a.m2 = self.w_sum.data_ptr(), self.mean.data_ptr(), self.m2.data_ptr()
-        a.exceed = self.exceed.data_ptr() if k else None
-        a.n_used, a.n_skipped = self.n_used.data_ptr(), self.n_skipped.data_ptr()
-        self._c = a
+        super().__init__(self.n, int(self.thresholds.size), self.device)
 
     def update(self, samples: torch.Tensor, weights: Optional[torch.Tensor] = None):
-        x = _rows(samples, self.engine.ndim, "Accumulator.update")
-        _launch(self.engine, x, _row_weights(weights, x, "Accumulator.update"), self.block, self, False)
+        x = _args.sample_rows(samples, self.engine.ndim, "Accumulator.update")
+        _launch(self.engine, x, _args.row_weights(weights, x, "Accumulator.update"), self.block, self, False)
         return self
 
     def result(self) -> dict:
         """mean, std (ddof 0), pull_mean = mean / sigma, exceed [n_thr, n] as fractions of the weight, sigma, z, thresholds,
         n_used, n_skipped, w_sum: numpy arrays of the block's n data (a datum no row was used for gives NaN)."""
         sigma = self.engine.resid_sigma(self.block)
+        mean, std = self.mean_std()
         w_sum = self.w_sum.cpu().numpy()
-        mean = np.where(w_sum > 0, self.mean.cpu().numpy(), np.nan)
         with np.errstate(invalid="ignore", divide="ignore"):
-            std = np.sqrt(self.m2.cpu().numpy() / w_sum)
             exceed = self.exceed.cpu().numpy() / w_sum[None, :]
         z = self.engine.sn_z if self.block == "sn" else self.engine.bao_z
         return dict(mean=mean, std=std, pull_mean=mean / sigma, exceed=exceed, sigma=sigma, z=None if z is None else z.copy(),
@@ -159,11 +137,10 @@ def _launch(engine, x: torch.Tensor, w: Optional[torch.Tensor], block: str, acc:
         return sample, blocks
     thr = acc.thresholds if acc is not None else np.empty(0)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
         L.check(L.lib().cf_resid_device(engine._h, x.data_ptr(), S, None if w is None else w.data_ptr(), L.RESID_BLOCKS[block],
-                                        thr.ctypes.data_as(C.c_void_p) if thr.size else None, int(thr.size),
+                                        _args.ptr(thr) if thr.size else None, int(thr.size),
                                         None if sample is None else sample.data_ptr(), None if blocks is None else blocks.data_ptr(),
-                                        None if acc is None else C.byref(acc._c), stream))
+                                        None if acc is None else C.byref(acc.c), _args.stream_of(dev)))
     return sample, blocks
 
 
@@ -172,7 +149,7 @@ def sample_stats(engine, samples: torch.Tensor, block: str = "sn"):
     row of samples [S, ndim] the residual statistics in the order of ``COLUMNS`` and the chi^2 shares in the order of
     ``BLOCK_COLUMNS``.  A row's values do not depend on S or on its position."""
     _check_engine(engine, block, "sample_stats")
-    return _launch(engine, _rows(samples, engine.ndim, "sample_stats"), None, block, None, True)
+    return _launch(engine, _args.sample_rows(samples, engine.ndim, "sample_stats"), None, block, None, True)
 
 
 def datum_stats(engine, samples: torch.Tensor, weights: Optional[torch.Tensor] = None, block: str = "sn",
@@ -183,8 +160,8 @@ def datum_stats(engine, samples: torch.Tensor, weights: Optional[torch.Tensor] =
     _check_engine(engine, block, "datum_stats")
     if chunk is not None and int(chunk) < 1:
         raise ValueError("chunk must be >= 1")
-    x = _rows(samples, engine.ndim, "datum_stats")
-    w = _row_weights(weights, x, "datum_stats")
+    x = _args.sample_rows(samples, engine.ndim, "datum_stats")
+    w = _args.row_weights(weights, x, "datum_stats")
     acc = Accumulator(engine, block, thresholds, device=x.device)
     step = x.shape[0] if chunk is None else int(chunk)
     for s0 in range(0, x.shape[0], max(step, 1)):
@@ -197,9 +174,9 @@ def report(engine, samples: torch.Tensor, weights: Optional[torch.Tensor] = None
     """Both kernels' outputs from one pass over the rows: dict(stats [S, ncol] and chi2_blocks [S, 10] on the device, columns,
     datum = the dict of ``datum_stats``)."""
     _check_engine(engine, block, "report")
-    x = _rows(samples, engine.ndim, "report")
+    x = _args.sample_rows(samples, engine.ndim, "report")
     acc = Accumulator(engine, block, thresholds, device=x.device)
-    stats, blocks = _launch(engine, x, _row_weights(weights, x, "report"), block, acc, True)
+    stats, blocks = _launch(engine, x, _args.row_weights(weights, x, "report"), block, acc, True)
     return dict(stats=stats, chi2_blocks=blocks, columns=COLUMNS, datum=acc.result())
 
 
@@ -226,10 +203,10 @@ def summary(engine, samples: torch.Tensor, weights: Optional[torch.Tensor] = Non
     n_data: the data the dof counts (default: those of the block).  stats: the [S, ncol] of ``sample_stats`` if already
     computed."""
     n = _check_engine(engine, block, "summary")
-    x = _rows(samples, engine.ndim, "summary")
+    x = _args.sample_rows(samples, engine.ndim, "summary")
     if x.shape[0] < 1:
         raise ValueError("summary needs at least one sample")
-    w = _row_weights(weights, x, "summary")
+    w = _args.row_weights(weights, x, "summary")
     c = center_of(x, w, center)
     at, _ = sample_stats(engine, torch.from_numpy(np.ascontiguousarray(c[None, :])).to(x.device), block)
     at = at.cpu().numpy()[0]

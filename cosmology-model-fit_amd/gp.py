@@ -28,6 +28,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
+from ._args import ptr, stream_of
 
 NDIM = L.CF_GP_NDIM
 NAMES = ("mean", "output_scale", "length_scale", "noise_scale")
@@ -40,9 +41,6 @@ def default_bounds(z_max: float) -> np.ndarray:
         raise ValueError("the default box needs max z > 0 (length scale in (max z, 3 max z)); pass bounds=")
     return np.array([[-2.0, 2.0], [0.05, 20.0], [z_max, 3.0 * z_max], [0.05, 4.0]])
 
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _z_star(z_star) -> np.ndarray:
@@ -152,7 +150,7 @@ class HubbleGP:
         """log_ml (normalised units), quad = r^T K^-1 r and logdet = log|K| of the rows of theta."""
         th = self._rows(theta)
         out, parts = np.empty(th.shape[0]), np.empty((th.shape[0], 2))
-        L.check(L.lib().cf_gp_mll(self._handle("parts"), _ptr(th), th.shape[0], _ptr(out), _ptr(parts)))
+        L.check(L.lib().cf_gp_mll(self._handle("parts"), ptr(th), th.shape[0], ptr(out), ptr(parts)))
         return dict(log_ml=out, quad=parts[:, 0], logdet=parts[:, 1])
 
     def log_marginal_likelihood(self, theta):
@@ -160,7 +158,7 @@ class HubbleGP:
         [W, 4]; -inf outside the box."""
         th = self._rows(theta)
         out = np.empty(th.shape[0])
-        L.check(L.lib().cf_gp_mll(self._handle("log_marginal_likelihood"), _ptr(th), th.shape[0], _ptr(out), None))
+        L.check(L.lib().cf_gp_mll(self._handle("log_marginal_likelihood"), ptr(th), th.shape[0], ptr(out), None))
         out = out - self.log_norm
         return float(out[0]) if np.ndim(theta) == 1 else out
 
@@ -168,7 +166,7 @@ class HubbleGP:
         """[S, nz, 5] = (mean, var, dmean, dvar, cov_fd) of the normalised process: the kernel's own output."""
         th, zs = self._rows(theta), _z_star(z_star)
         out = np.empty((th.shape[0], zs.size, 5))
-        L.check(L.lib().cf_gp_predict(self._handle("predict"), _ptr(th), th.shape[0], _ptr(zs), zs.size, _noise(noise), _ptr(out)))
+        L.check(L.lib().cf_gp_predict(self._handle("predict"), ptr(th), th.shape[0], ptr(zs), zs.size, _noise(noise), ptr(out)))
         return out
 
     def _to_physical(self, zs, mean, var, dmean, dvar, cov, xp=np) -> dict:
@@ -212,7 +210,7 @@ class HubbleGP:
             out = torch.empty(theta.shape[0], dtype=torch.float64, device=theta.device)
             if theta.shape[0]:
                 L.check(lib.cf_gp_mll_device(h, theta.data_ptr(), theta.shape[0], out.data_ptr(), None,
-                                             torch.cuda.current_stream(theta.device).cuda_stream))
+                                             stream_of(theta.device)))
                 out -= self.log_norm
             return out
 
@@ -238,7 +236,7 @@ class HubbleGP:
         out = torch.empty((x.shape[0], zd.shape[0], 5), dtype=torch.float64, device=x.device)
         with torch.cuda.device(x.device):
             L.check(L.lib().cf_gp_predict_device(h, x.data_ptr(), x.shape[0], zd.data_ptr(), zd.shape[0], noise, out.data_ptr(),
-                                                 torch.cuda.current_stream(x.device).cuda_stream))
+                                                 stream_of(x.device)))
         return out
 
     def marginal_predict(self, samples, z_star, weights=None, noise: float = 0.0, max_bytes: int = 2**28) -> dict:

@@ -33,14 +33,11 @@ import torch
 
 from . import _lib as L
 from . import fit_report as F
+from ._args import ptr, row_weights, sample_rows, stream_of
 
 COLUMNS = L.INFL_COLUMNS
 WANT = ("contrib", "z", "loo", "g")
 _REPORT_KEYS = ("weights", "block", "thresholds")
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 class Precision:
@@ -54,7 +51,7 @@ class Precision:
         self.n, self.device = int(m.shape[0]), int(device)
         self._p = C.c_void_p()
         create = L.lib().cf_prec_create if from_factor else L.lib().cf_prec_create_inv
-        L.check(create(_ptr(m), self.n, self.n, self.device, C.byref(self._p)))
+        L.check(create(ptr(m), self.n, self.n, self.device, C.byref(self._p)))
 
     def close(self):
         if getattr(self, "_p", None) is not None and self._p.value:
@@ -70,7 +67,7 @@ class Precision:
     def diag(self) -> np.ndarray:
         """K_ii, [n] numpy."""
         out = np.empty(self.n)
-        L.check(L.lib().cf_prec_diag(self._p, _ptr(out)))
+        L.check(L.lib().cf_prec_diag(self._p, ptr(out)))
         return out
 
     def loo_sigma(self) -> np.ndarray:
@@ -92,12 +89,8 @@ class Precision:
         if S:
             with torch.cuda.device(rows.device):
                 L.check(L.lib().cf_prec_apply_device(self._p, rows.data_ptr(), rows.stride(0), S, g.data_ptr(), g.stride(0),
-                                                     torch.cuda.current_stream(rows.device).cuda_stream))
+                                                     stream_of(rows.device)))
         return g
-
-
-def _check_engine(engine, block: str, what: str) -> int:
-    return F._check_engine(engine, block, what)
 
 
 def _to_device(a: np.ndarray) -> torch.Tensor:
@@ -114,7 +107,7 @@ def _theta_rows(engine, theta, what: str) -> torch.Tensor:
         theta = _to_device(th)
     elif theta.dim() == 1:
         theta = theta[None, :]
-    return F._rows(theta, engine.ndim, what)
+    return sample_rows(theta, engine.ndim, what)
 
 
 def set_library_chunk(engine, rows: int = 0):
@@ -123,30 +116,8 @@ def set_library_chunk(engine, rows: int = 0):
     L.check(L.lib().cf_infl_set_chunk(engine._h, int(rows)))
 
 
-class _Acc:
-    """The arrays of one ``cf_resid_acc`` on a device."""
-
-    def __init__(self, n: int, n_thr: int, device):
-        f64 = dict(dtype=torch.float64, device=device)
-        self.w_sum, self.mean, self.m2 = (torch.zeros(n, **f64) for _ in range(3))
-        self.exceed = torch.zeros((n_thr, n), **f64)
-        self.n_used, self.n_skipped = (torch.zeros(n, dtype=torch.int64, device=device) for _ in range(2))
-        a = L.cf_resid_acc()
-        a.struct_size, a.n, a.n_thr = C.sizeof(L.cf_resid_acc), n, n_thr
-        a.w_sum, a.mean, a.m2 = self.w_sum.data_ptr(), self.mean.data_ptr(), self.m2.data_ptr()
-        a.exceed = self.exceed.data_ptr() if n_thr else None
-        a.n_used, a.n_skipped = self.n_used.data_ptr(), self.n_skipped.data_ptr()
-        self.c = a
-
-    def mean_std(self):
-        w_sum = self.w_sum.cpu().numpy()
-        mean = np.where(w_sum > 0, self.mean.cpu().numpy(), np.nan)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return mean, np.sqrt(self.m2.cpu().numpy() / w_sum)
-
-
 def _launch(engine, x: torch.Tensor, w: Optional[torch.Tensor], block: str, want: Sequence[str], want_sample: bool,
-            thresholds: np.ndarray, acc_z: Optional[_Acc], acc_contrib: Optional[_Acc]) -> dict:
+            thresholds: np.ndarray, acc_z: Optional[F.DatumAcc], acc_contrib: Optional[F.DatumAcc]) -> dict:
     """One cf_infl_device call on torch's current stream (x and w checked by the caller)."""
     n = int(engine.n_sn if block == "sn" else engine.n_bao)
     S, dev = x.shape[0], x.device
@@ -161,11 +132,10 @@ def _launch(engine, x: torch.Tensor, w: Optional[torch.Tensor], block: str, want
         setattr(out, k, t.data_ptr())
     prec = engine.precision(block)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
         L.check(L.lib().cf_infl_device(engine._h, prec._p, x.data_ptr(), S, None if w is None else w.data_ptr(), L.RESID_BLOCKS[block],
-                                       thresholds.ctypes.data_as(C.c_void_p) if thresholds.size else None, int(thresholds.size),
+                                       ptr(thresholds) if thresholds.size else None, int(thresholds.size),
                                        C.byref(out) if res else None, None if acc_z is None else C.byref(acc_z.c),
-                                       None if acc_contrib is None else C.byref(acc_contrib.c), stream))
+                                       None if acc_contrib is None else C.byref(acc_contrib.c), stream_of(dev)))
     return res
 
 
@@ -178,7 +148,7 @@ def rows(engine, theta, block: str = "sn", want: Sequence[str] = WANT) -> dict:
     [S, n] on the device, and ``sample``: the per-sample table as named columns [S] (``COLUMNS``: chi2 = sum_i contrib_i, the
     largest |z_i| and its index, the largest deletion drop g_i^2 / K_ii and its index).  Asynchronous on torch's current stream;
     a row's values do not depend on S or on its position."""
-    _check_engine(engine, block, "influence.rows")
+    F._check_engine(engine, block, "influence.rows")
     want = tuple(want)
     unknown = set(want) - set(WANT)
     if unknown:
@@ -194,18 +164,18 @@ class Accumulator:
     chain with ``update`` (the result is the same bits for every cut), read it with ``result``."""
 
     def __init__(self, engine, block: str = "sn", thresholds: Sequence[float] = (2.0, 3.0), device=None):
-        self.n = _check_engine(engine, block, "influence.Accumulator")
+        self.n = F._check_engine(engine, block, "influence.Accumulator")
         self.engine, self.block, self.thresholds = engine, block, F._thresholds(thresholds)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.z = _Acc(self.n, int(self.thresholds.size), self.device)
-        self.contrib = _Acc(self.n, 0, self.device)
+        self.z = F.DatumAcc(self.n, int(self.thresholds.size), self.device)
+        self.contrib = F.DatumAcc(self.n, 0, self.device)
 
     def update(self, samples: torch.Tensor, weights: Optional[torch.Tensor] = None, want_sample: bool = False):
         """Continue over the rows of samples; returns the per-sample table [S, len(COLUMNS)] when want_sample, else None."""
-        x = F._rows(samples, self.engine.ndim, "influence.Accumulator.update")
+        x = sample_rows(samples, self.engine.ndim, "influence.Accumulator.update")
         if x.device != self.device:
             raise ValueError("the accumulator lives on another device than the samples")
-        w = F._row_weights(weights, x, "influence.Accumulator.update")
+        w = row_weights(weights, x, "influence.Accumulator.update")
         return _launch(self.engine, x, w, self.block, (), want_sample, self.thresholds, self.z, self.contrib).get("sample")
 
     def result(self) -> dict:
@@ -261,7 +231,7 @@ def attribution(engine, theta_a, theta_b, block: str = "sn", order=None) -> dict
     permutation of the cumulative sum: ascending redshift, or the one given), redshift [n] in that order, cumulative [n] =
     cumsum(delta[order]), total = chi2(theta_a) - chi2(theta_b) of the block (paired rows: the mean; total_rows [S] has every
     pair's), and chi2_a, chi2_b [S].  sum_i delta_i = total up to rounding."""
-    n = _check_engine(engine, block, "influence.attribution")
+    n = F._check_engine(engine, block, "influence.attribution")
     xa = _theta_rows(engine, theta_a, "influence.attribution")
     xb = _theta_rows(engine, theta_b, "influence.attribution")
     if xa.shape != xb.shape:

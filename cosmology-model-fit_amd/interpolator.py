@@ -2,19 +2,14 @@
 Drop-in for the reference's ``interpolator.py`` (same function names and argument order), evaluated
 by the HIP ``interp_kernel`` through the C-ABI.  interpolator.py:111-119.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib as L
+from ._args import ptr
 
 
 def _prep(*arrs):
     return [np.ascontiguousarray(a, dtype=np.float64) for a in arrs]
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def interp_hermite(xq, x, y, y_prime):
@@ -23,7 +18,7 @@ def interp_hermite(xq, x, y, y_prime):
     if not (x.size == y.size == yp.size):
         raise ValueError("x, y, y_prime must have the same length")
     out = np.empty_like(xq)
-    L.check(L.lib().cf_interp_hermite(_p(xq), xq.size, _p(x), _p(y), _p(yp), x.size, _p(out)))
+    L.check(L.lib().cf_interp_hermite(ptr(xq), xq.size, ptr(x), ptr(y), ptr(yp), x.size, ptr(out)))
     return out
 
 
@@ -33,5 +28,5 @@ def interp_pchip(xq, x, y):
     if x.size != y.size:
         raise ValueError("x and y must have the same length")
     out = np.empty_like(xq)
-    L.check(L.lib().cf_interp_pchip(_p(xq), xq.size, _p(x), _p(y), x.size, _p(out)))
+    L.check(L.lib().cf_interp_pchip(ptr(xq), xq.size, ptr(x), ptr(y), x.size, ptr(out)))
     return out

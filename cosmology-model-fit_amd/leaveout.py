@@ -33,14 +33,12 @@ import torch
 from . import _lib as L
 from . import fit_report as F
 from . import influence as I
+from ._args import on_device, ptr, row_weights, sample_rows, stream_of
 
 PIECE = 65536  # rows of g formed at a time by group_chi2
 KHAT_RELIABLE = 0.7  # Vehtari, Simpson, Gelman, Yao & Gabry, "Pareto smoothed importance sampling": the published threshold
 _LGO_KEYS = ("groups", "block", "weights", "columns", "theta_ref", "names")
 
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 # ---- groups ---------------------------------------------------------------------------------------------------------------------
@@ -102,7 +100,7 @@ def check_groups(groups, n: int, kdiag=None):
     ``CosmofitError`` naming the group."""
     offsets, idx = pack_groups(groups)
     kd = None if kdiag is None else np.ascontiguousarray(kdiag, dtype=np.float64)
-    L.check(L.lib().cf_group_check_args(int(n), None if kd is None else _ptr(kd), len(offsets) - 1, _ptr(offsets), _ptr(idx)))
+    L.check(L.lib().cf_group_check_args(int(n), None if kd is None else ptr(kd), len(offsets) - 1, ptr(offsets), ptr(idx)))
     return offsets, idx
 
 
@@ -138,8 +136,8 @@ class Groups:
 
     def _build(self, prec):
         self.device = prec.device
-        L.check(L.lib().cf_group_check_args(self.n, _ptr(prec.diag()), self.n_groups, _ptr(self.offsets), _ptr(self.idx)))
-        L.check(L.lib().cf_group_create(prec._p, self.n_groups, _ptr(self.offsets), _ptr(self.idx), C.byref(self._p)))
+        L.check(L.lib().cf_group_check_args(self.n, ptr(prec.diag()), self.n_groups, ptr(self.offsets), ptr(self.idx)))
+        L.check(L.lib().cf_group_create(prec._p, self.n_groups, ptr(self.offsets), ptr(self.idx), C.byref(self._p)))
 
     def close(self):
         if getattr(self, "_p", None) is not None and self._p.value:
@@ -164,7 +162,7 @@ class Groups:
     def info(self) -> dict:
         """n, n_groups, device, max_m, n_idx, bytes (held on the device), m [G], pitch [G] (m rounded up to 16)."""
         out, m, pitch = np.zeros(6, dtype=np.int64), np.zeros(self.n_groups, dtype=np.int64), np.zeros(self.n_groups, dtype=np.int64)
-        L.check(L.lib().cf_group_info(self._p, _ptr(out), _ptr(m), _ptr(pitch)))
+        L.check(L.lib().cf_group_info(self._p, ptr(out), ptr(m), ptr(pitch)))
         return dict(zip(("n", "n_groups", "device", "max_m", "n_idx", "bytes"), out.tolist()), m=m, pitch=pitch)
 
     def quad(self, g: torch.Tensor, S: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -181,7 +179,7 @@ class Groups:
         if S:
             with torch.cuda.device(g.device):
                 L.check(L.lib().cf_group_quad_device(self._p, g.data_ptr(), g.stride(0), S, q.data_ptr(), q.stride(0),
-                                                     torch.cuda.current_stream(g.device).cuda_stream))
+                                                     stream_of(g.device)))
         return q
 
 
@@ -285,7 +283,7 @@ def _check_reweight(log_w, x, base_weights, names, what="leaveout.reweight"):
 def reweight_record(lw: torch.Tensor, x: torch.Tensor, w0: Optional[torch.Tensor], pivot: np.ndarray) -> torch.Tensor:
     """The raw records [G, CF_RW_NCOL(ncol)] of ``cf_reweight_device`` on the device (inputs as ``_check_reweight`` returns them,
     on an MI355X), asynchronous on torch's current stream."""
-    F.chain_stats._on_device(x, "leaveout.reweight")
+    on_device(x, "leaveout.reweight")
     lw = lw if lw.stride(1) == 1 else lw.contiguous()
     x = x if x.stride(1) == 1 else x.contiguous()
     w0 = None if w0 is None else w0.contiguous()
@@ -294,8 +292,8 @@ def reweight_record(lw: torch.Tensor, x: torch.Tensor, w0: Optional[torch.Tensor
     out = torch.empty((G, L.rw_ncol(ncol)), dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
         L.check(L.lib().cf_reweight_device(lw.data_ptr(), lw.stride(0), S, G, None if w0 is None else w0.data_ptr(), x.data_ptr(),
-                                           x.stride(0), ncol, _ptr(pivot), out.data_ptr(),
-                                           torch.cuda.current_stream(x.device).cuda_stream))
+                                           x.stride(0), ncol, ptr(pivot), out.data_ptr(),
+                                           stream_of(x.device)))
     return out
 
 
@@ -374,7 +372,7 @@ def reweight(log_w, x, base_weights=None, names=None) -> dict:
 
     The sums run on the device in a fixed order (``cf_reweight_device``); the same inputs give the same bits."""
     lw, x, w0, names = _check_reweight(log_w, x, base_weights, names)
-    F.chain_stats._on_device(x, "leaveout.reweight")
+    on_device(x, "leaveout.reweight")
     ok = torch.isfinite(x).all(dim=1)
     wb = torch.ones(x.shape[0], dtype=torch.float64, device=x.device) if w0 is None else torch.where(torch.isfinite(w0) & (w0 >= 0), w0, torch.zeros_like(w0))
     wb = torch.where(ok, wb, torch.zeros_like(wb))
@@ -409,12 +407,12 @@ def leave_group_out(engine, chain, groups, block: str = "sn", weights=None, colu
     A group whose removal moves the posterior far has few effective samples and khat >= 0.7: then the reweighted numbers are
     not to be trusted and a direct run on the reduced data is the answer (examples/union3_leaveout.py shows both)."""
     n = F._check_engine(engine, block, "leaveout.leave_group_out")
-    x = F._rows(chain, engine.ndim, "leaveout.leave_group_out") if isinstance(chain, torch.Tensor) and chain.dim() == 2 else None
+    x = sample_rows(chain, engine.ndim, "leaveout.leave_group_out") if isinstance(chain, torch.Tensor) and chain.dim() == 2 else None
     if x is None:
         raise ValueError(f"leaveout.leave_group_out takes the chain as a float64 tensor [S, {engine.ndim}] on an MI355X")
     if x.shape[0] < 1:
         raise ValueError("leaveout.leave_group_out needs at least one row")
-    w0 = F._row_weights(weights, x, "leaveout.leave_group_out")
+    w0 = row_weights(weights, x, "leaveout.leave_group_out")
     cols = x
     if columns is not None:
         extra = _as_columns(columns, "leaveout.leave_group_out", "columns")

@@ -21,14 +21,14 @@ The inputs are float64 tensors on an MI355X; there is no CPU fallback: CPU tenso
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from .chain_stats import _on_device, percentile
+from ._args import float64_tensor, on_device, ptr, stream_of
+from .chain_stats import percentile
 
 MAX_BINS, MAX_NDIM, MAX_PAIRS = _lib.CF_MARG_MAX_BINS, _lib.CF_MARG_MAX_NDIM, _lib.CF_MARG_MAX_PAIRS
 
@@ -106,10 +106,7 @@ def _weighted_quantile(x: torch.Tensor, w: torch.Tensor, q) -> np.ndarray:
 # ---- argument checks --------------------------------------------------------------------------------------------------
 def _samples(samples, what: str) -> torch.Tensor:
     """Shape and type first, the device last: a wrong argument is reported the same with and without a GPU."""
-    if not isinstance(samples, torch.Tensor):
-        raise ValueError(f"{what} takes a tensor on an MI355X (there is no CPU implementation to fall back to)")
-    if samples.dtype != torch.float64:
-        raise ValueError(f"{what} takes float64")
+    samples = float64_tensor(samples, what)
     if samples.dim() != 2 or samples.shape[0] < 1 or not 1 <= samples.shape[1] <= MAX_NDIM:
         raise ValueError(f"{what} takes samples [n, k] with n >= 1 and 1 <= k <= {MAX_NDIM}")
     if samples.shape[0] > 2**31 - 1:
@@ -132,7 +129,7 @@ def _weights(weights, n: int, what: str) -> Tuple[torch.Tensor, float]:
 
 
 def _device(x: torch.Tensor, w: Optional[torch.Tensor], what: str) -> torch.Tensor:
-    x = _on_device(x, what)
+    x = on_device(x, what)
     if w is not None and w.device != x.device:
         raise ValueError("weights must be on the device of the samples")
     return x.contiguous()
@@ -231,14 +228,14 @@ def histograms(samples: torch.Tensor, bins: int = 100, range=None, weights: Opti
     edges = np.stack([np.linspace(lo, hi, bins + 1) for lo, hi in lo_hi])
     L, lib = _lib, _lib.lib()
     with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
+        stream = stream_of(x.device)
         d_edges = torch.from_numpy(edges).to(x.device)
         idx = torch.empty((n, k), dtype=torch.uint8, device=x.device)
         L.check(lib.cf_marg_bin(x.data_ptr(), n, k, d_edges.data_ptr(), bins, idx.data_ptr(), stream))
         h1 = torch.empty((k, bins), dtype=torch.int64, device=x.device)
         h2 = torch.empty((len(pr), bins, bins), dtype=torch.int64, device=x.device)
         L.check(lib.cf_marg_hist(idx.data_ptr(), None if w is None else w.data_ptr(), w_max, n, k, bins,
-                                 pr.ctypes.data_as(C.c_void_p), len(pr), h1.data_ptr(), h2.data_ptr() if len(pr) else None,
+                                 ptr(pr), len(pr), h1.data_ptr(), h2.data_ptr() if len(pr) else None,
                                  int(n_segments), stream))
     if w is not None:
         scale = np.ldexp(w_max, -fixed_point_shift(n))

@@ -36,6 +36,7 @@ import torch
 
 from . import _lib as L
 from . import optimize as opt
+from ._args import require_gpu, single_device_engine, stream_of
 from .ensemble import _U64, _mix_int
 
 BLOCKS = ("sn", "bao", "cmb")
@@ -60,14 +61,10 @@ def set_library_chunk(engine, rows: int = 0):
 
 
 # ---- checks that need no device (the CPU tests reach them) -------------------------------------------------------------
-def _check_engine(engine, what: str) -> dict:
-    info, md = getattr(engine, "model_info", None), getattr(engine, "mock_data", None)
-    if info is None or md is None:
-        raise ValueError(f"{what} takes a LikelihoodEngine (or a likelihood mirror's .engine)")
-    if info["quasar"]:
-        raise ValueError(f"{what}: a quasar engine has no accessor path to take the residuals from")
-    if info["multi_device"]:
-        raise ValueError(f"{what}: the engine spans several devices; use one engine per device")
+def _mock_data(engine, what: str) -> dict:
+    """``engine.mock_data`` of an engine that passes the gate (one without it is refused as no LikelihoodEngine)."""
+    md = getattr(engine, "mock_data", None)
+    single_device_engine(engine if md is not None else None, what)
     return md
 
 
@@ -217,7 +214,7 @@ class MockSet:
     def from_shifts(cls, engine, sn=None, bao=None, cmb=None, theta_fid=None) -> "MockSet":
         """The set whose mock k has the data ``obs + sn[k]``, ``val + bao[k]``, ``prior + cmb[k]`` (arrays or tensors [K, n_b];
         None: the block keeps its observed data).  theta_fid: the start ``best_fits`` gives every mock (optional)."""
-        md = _check_engine(engine, "MockSet.from_shifts")
+        md = _mock_data(engine, "MockSet.from_shifts")
         given = {b: d for b, d in zip(BLOCKS, (sn, bao, cmb)) if d is not None}
         if not given:
             raise ValueError("MockSet.from_shifts needs the shifts of at least one block")
@@ -263,7 +260,7 @@ class MockSet:
         that the mock data are model(theta_fid) + noise.  Components of the BAO / CMB blocks whose row of the inverse covariance
         is zero stay unshifted.  A likelihood with cosmic chronometers, a growth-rate block or ``chi2_gauss`` terms raises unless
         keep_observed names them ("cc", "fs8", "chi2_gauss"): those keep their observed data in every mock."""
-        md = _check_engine(engine, "MockSet.draw")
+        md = _mock_data(engine, "MockSet.draw")
         _check_unshiftable(md, keep_observed)
         have = _present(engine, md)
         blocks = list(have) if blocks is None else list(blocks)
@@ -325,7 +322,7 @@ class MockSet:
         cross = torch.empty((S, 3), dtype=torch.float64, device=self.device) if want_cross else None
         if S:
             with torch.cuda.device(self.device):
-                stream = torch.cuda.current_stream(self.device).cuda_stream
+                stream = stream_of(self.device)
                 L.check(L.lib().cf_mock_eval_device(self.engine._h, C.byref(self._c), theta.data_ptr(), S, mock.data_ptr(), int(kind),
                                                     out.data_ptr(), None if cross is None else cross.data_ptr(), stream))
         return out, cross
@@ -367,7 +364,7 @@ class MockSet:
             fid[i] = v
         if not np.all((fid > b[:, 0]) & (fid < b[:, 1])):
             raise ValueError("theta_fid (with the fixed values) must lie strictly inside the bounds")
-        Lm, lib = opt._require_gpu("maximize")
+        Lm, lib = require_gpu("optimize.maximize")
         K, P = self.n_mocks, self.n_mocks * n_starts
         if all_fixed:  # a nested model without a free parameter: nothing to maximise, its chi^2 is the chi^2 at the point
             x = np.tile(fid, (K, 1))
@@ -419,5 +416,5 @@ def normals(key: int, K: int, n: int, k0: int = 0, device=None) -> torch.Tensor:
     out = torch.empty((K, n), dtype=torch.float64, device=dev)
     if K:
         with torch.cuda.device(dev):
-            L.check(lib.cf_mock_normals(key & _U64, k0, K, n, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            L.check(lib.cf_mock_normals(key & _U64, k0, K, n, out.data_ptr(), stream_of(dev)))
     return out

@@ -57,6 +57,7 @@ from typing import Callable, Sequence, Tuple
 
 import numpy as np
 
+from ._args import stream_of
 from .ensemble import _U64, _mix_int, uniform01_scalar
 
 # ---- random-stream keys ----------------------------------------------------------------------------------------------
@@ -238,11 +239,6 @@ class DeviceNestedSampler:
         self._post_dev = None  # (the results they belong to, points, weights) on the device, for marginals() / mean_std()
 
     # ---- device steps --------------------------------------------------------------------------------------------
-    def _stream(self):
-        import torch
-
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _loglike(self, theta):
         import torch
 
@@ -258,7 +254,7 @@ class DeviceNestedSampler:
 
         L, lib = self.L, self.lib
         L.check(lib.cf_ns_prior_draw(C.byref(self._c_prior), self.n_live, ns_key(self.seed, 0, 0), self._live_u.data_ptr(),
-                                     self._live_th.data_ptr(), self._stream()))
+                                     self._live_th.data_ptr(), stream_of(self.device)))
         lv = self._loglike(self._live_th)
         bad = ~torch.isfinite(lv)
         self.n_nonfinite_start = int(bad.sum())
@@ -284,7 +280,7 @@ class DeviceNestedSampler:
         surv = torch.sort(order[m:]).values
         su, sth, sl = (self._live_u.index_select(0, surv), self._live_th.index_select(0, surv),
                        self._live_l.index_select(0, surv))
-        ns, stream, p = n - m, self._stream(), C.byref(self._c_prior)
+        ns, stream, p = n - m, stream_of(self.device), C.byref(self._c_prior)
         wu, wth, wl, pu, pth, ok = self._wu, self._wth, self._wl, self._pu, self._pth, self._ok
         L.check(lib.cf_ns_walk_start(su.data_ptr(), sth.data_ptr(), sl.data_ptr(), ns, d, m, ns_key(self.seed, self._it, 0),
                                      wu.data_ptr(), wth.data_ptr(), wl.data_ptr(), stream))

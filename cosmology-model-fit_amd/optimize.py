@@ -48,6 +48,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
+from ._args import require_gpu, stream_of
 from .ensemble import _U64, _mix_int
 
 # ---- random-stream keys ----------------------------------------------------------------------------------------------
@@ -252,18 +253,6 @@ def _params(b: np.ndarray, free: list, o: dict):
     return p
 
 
-def _require_gpu(what: str):
-    import torch
-
-    from . import _lib as L
-
-    lib = L.lib()  # raises if the HIP library is missing
-    if lib.cf_device_count() < 1 or not torch.cuda.is_available():
-        raise L.CosmofitError(-2, f"optimize.{what} runs in the library's HIP kernels: no GPU is visible (there is no tensor "
-                                  "fallback)")
-    return L, lib
-
-
 # ---- the device loop -------------------------------------------------------------------------------------------------
 class _State:
     """Per-problem device state (cf_opt_state) of B problems."""
@@ -308,7 +297,7 @@ def _run(log_prob, p, u, theta, L, lib, problem_index: bool = False) -> Optimize
 
     B, d, nf, K = u.shape[0], p.ndim, p.n_free, p.n_trials
     dev = u.device
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    stream = stream_of(dev)
     st = _State(B, d, dev)
     st.u.copy_(u)
     f = _call(log_prob, theta, torch.arange(B, dtype=torch.int32, device=dev) if problem_index else None)
@@ -351,7 +340,7 @@ def _starts(p, x0: np.ndarray, key: Optional[int], L, lib):
     x = torch.from_numpy(np.ascontiguousarray(x0)).to(dev)
     u, th = torch.empty_like(x), torch.empty_like(x)
     L.check(lib.cf_opt_starts(C.byref(p), x.shape[0], x.data_ptr(), 0 if key is None else key, 0 if key is None else 1,
-                              u.data_ptr(), th.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+                              u.data_ptr(), th.data_ptr(), stream_of(dev)))
     return u, th
 
 
@@ -371,7 +360,7 @@ def maximize(log_prob: Callable, bounds, x0, *, free=None, h=1e-6, n_trials=4, g
     fr = _free_list(free, ndim)
     o = _options(h, n_trials, gtol, gtol_rel, max_iter, c1)
     x = _as_rows(x0, ndim)
-    L, lib = _require_gpu("maximize")
+    L, lib = require_gpu("optimize.maximize")
     p = _params(b, fr, o)
     u, th = _starts(p, x, None, L, lib)
     return _run(log_prob, p, u, th, L, lib, bool(problem_index))
@@ -419,7 +408,7 @@ def best_fit(log_prob: Callable, bounds, *, n_starts=32, seed=0, x0=None, fixed=
     rand = np.tile(0.5 * (b[:, 0] + b[:, 1]), (n_starts, 1))
     for i, v in fx.items():
         given[:, i], rand[:, i] = v, v
-    L, lib = _require_gpu("best_fit")
+    L, lib = require_gpu("optimize.best_fit")
     import torch
 
     p = _params(b, fr, o)
@@ -467,7 +456,7 @@ def profile(log_prob: Callable, bounds, index, grid, *, n_starts=8, seed=0, best
     if n_starts < 1:
         raise ValueError("n_starts must be >= 1")
     o = _options(**{**DEFAULTS, **options})
-    L, lib = _require_gpu("profile")
+    L, lib = require_gpu("optimize.profile")
     import torch
 
     if best is None:

@@ -28,6 +28,7 @@ import torch
 
 from . import _lib as L
 from . import derived, marginals
+from ._args import ptr, sample_rows, stream_of
 
 FDE = {"wcdm": L.CF_FDE_WCDM, "thawing": L.CF_FDE_THAWING, "cpl": L.CF_FDE_CPL}
 MAX_NQ = L.CF_FIELD_MAX_NQ
@@ -212,7 +213,7 @@ def _unpack(out: dict, qa, qphi, qt, wrap) -> dict:
 def _rows(model: Model, samples, what: str) -> torch.Tensor:
     if not isinstance(model, Model):
         raise ValueError(f"{what} takes a quintessence.Model")
-    return derived._rows(samples, model.ndim, what)
+    return sample_rows(samples, model.ndim, what)
 
 
 def reconstruct(model: Model, samples: torch.Tensor, a=None, phi=None, t=None, _want=None) -> dict:
@@ -233,11 +234,10 @@ def reconstruct(model: Model, samples: torch.Tensor, a=None, phi=None, t=None, _
     dev = x.device
     tdt = {np.float64: torch.float64, np.int32: torch.int32}
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
         out = _call(model, x.data_ptr(), x.shape[0], qa, qphi, qt,
                     alloc=lambda shape, dt: torch.empty(shape, dtype=tdt[dt], device=dev),
                     upload=lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev),
-                    ptr=lambda b: b.data_ptr(), stream=stream, want=_want)
+                    ptr=lambda b: b.data_ptr(), stream=stream_of(dev), want=_want)
     return _unpack(out, qa, qphi, qt, lambda v: torch.from_numpy(v).to(dev))
 
 
@@ -249,9 +249,8 @@ def reconstruct_host(model: Model, theta, a=None, phi=None, t=None) -> dict:
     th = np.ascontiguousarray(theta, dtype=np.float64)
     if th.ndim != 2 or th.shape[1] != model.ndim:
         raise ValueError(f"theta must be [n, {model.ndim}]")
-    p = lambda b: b.ctypes.data_as(C.c_void_p)
-    out = _call(model, p(th), th.shape[0], qa, qphi, qt, alloc=lambda shape, dt: np.empty(shape, dtype=dt),
-                upload=lambda v: np.ascontiguousarray(v), ptr=p, stream=None, want=None)
+    out = _call(model, ptr(th), th.shape[0], qa, qphi, qt, alloc=lambda shape, dt: np.empty(shape, dtype=dt),
+                upload=lambda v: np.ascontiguousarray(v), ptr=ptr, stream=None, want=None)
     return _unpack(out, qa, qphi, qt, lambda v: v)
 
 

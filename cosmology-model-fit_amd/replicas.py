@@ -36,7 +36,8 @@ from typing import Callable
 import numpy as np
 import torch
 
-from .ensemble import (_KIND, _MOVE_STREAM, _U64, STRETCH_ONLY, _mix_int, stream_key, uniform01_scalar)
+from ._args import stream_of
+from .ensemble import _KIND, _U64, STRETCH_ONLY, ChainRecorder, _mix_int
 
 SWAP_STREAM = 253  # the swap uniforms: stream_key(seeds[c T + t], step, 0, 253); the moves use streams 0 .. 36, 254, 255
 
@@ -109,7 +110,7 @@ class NativeReplicaMoves:
     def split_step(self, e, move, n_splits, split, record=None):
         L, lib = self.L, self.lib
         kind = _KIND[move]
-        stream = torch.cuda.current_stream(e.x.device).cuda_stream
+        stream = stream_of(e.x.device)
         n = e.R * (e.w // n_splits)
         step, rnd = e.step_count & _U64, int(e.randomize_split)
         if kind == 2:
@@ -128,12 +129,14 @@ class NativeReplicaMoves:
                                          e._n_acc.data_ptr(), slot, l_slot, counts, stream))
 
     def swap(self, e, parity):
-        stream = torch.cuda.current_stream(e.x.device).cuda_stream
+        stream = stream_of(e.x.device)
         self.L.check(self.lib.cf_rep_swap(e.x.data_ptr(), e.logp.data_ptr(), e.C, e.T, e.w, e.ndim, self.beta.data_ptr(),
                                           self.base.data_ptr(), e.step_count & _U64, parity, e._n_swapped.data_ptr(), stream))
 
 
-class ReplicaEnsemble:
+class ReplicaEnsemble(ChainRecorder):
+    _native = NativeReplicaMoves
+
     def __init__(self, log_prob_fn: Callable, positions: torch.Tensor, *, seeds=None, seed: int = 42, moves=STRETCH_ONLY,
                  a: float = 2.0, de_sigma: float = 1e-5, de_splits: int = 3, randomize_split: bool = True, betas=None, bounds=None,
                  swap_every: int = 1, pass_replica: bool = False, moves_impl=None):
@@ -150,17 +153,11 @@ class ReplicaEnsemble:
         swap_every: swaps between neighbouring rungs at the start of every swap_every-th step (T > 1).
         pass_replica: call ``log_prob_fn(theta [n, ndim], replica [n] int32)`` (the hook for ``mocks.MockSet.log_prob``).
         moves_impl: None = the library's kernels (positions must live on a GPU); tests pass a tensor statement."""
-        names = set(_KIND)
-        if not moves or any(m not in names or wt <= 0 for m, wt in moves):
-            raise ValueError(f"moves must be a non-empty sequence of (name in {sorted(names)}, weight > 0)")
-        if de_splits not in (2, 3):
-            raise ValueError("de_splits must be 3 (emcee's DEMove) or 2")
+        self._set_moves(moves, de_splits)
         if positions.dim() != 3 or positions.dtype != torch.float64:
             raise ValueError("positions must be [R, w, ndim] float64")
-        tot = float(sum(wt for _, wt in moves))
-        self.moves = [(m, wt / tot) for m, wt in moves]
         self.R, self.w, self.ndim = (int(v) for v in positions.shape)
-        self.a, self.de_sigma, self.de_splits, self.randomize_split = a, de_sigma, de_splits, bool(randomize_split)
+        self.a, self.de_sigma, self.randomize_split = a, de_sigma, bool(randomize_split)
         self.seed, self.step_count = int(seed), 0
         self.seeds = [int(seed) + 1 + r for r in range(self.R)] if seeds is None else [int(s) for s in seeds]
         if len(self.seeds) != self.R:
@@ -206,10 +203,7 @@ class ReplicaEnsemble:
         self._n_swapped = torch.zeros(self.C * max(self.T - 1, 1), dtype=torch.int64, device=dev)
         self._swap_rounds = np.zeros(max(self.T - 1, 1), dtype=np.int64)
         self._n_steps = 0
-        self._chain = torch.empty((0, self.R, self.w, self.ndim), dtype=torch.float64, device=dev)
-        self._chain_logp = torch.empty((0, self.R, self.w), dtype=torch.float64, device=dev)
-        self._iteration, self._mcmc_steps = 0, 0
-        self._walker_acc = torch.zeros(self.R * self.w, dtype=torch.int64, device=dev)
+        self._new_record((self.R, self.w), torch.float64)  # the chain is [n, R, w, ndim]: the layout of an emcee chain of R w walkers
         if moves_impl is None:
             if not self.x.is_cuda:
                 raise RuntimeError("ReplicaEnsemble runs its moves in the library's HIP kernels: the positions must be on an "
@@ -218,9 +212,6 @@ class ReplicaEnsemble:
         self.impl = moves_impl
 
     # ---- plumbing ---------------------------------------------------------------------------------------------------
-    def _splits_of(self, move: str) -> int:
-        return self.de_splits if move == "de" else 2
-
     def _call(self, theta: torch.Tensor, n_splits: int) -> torch.Tensor:
         """The callable on the rows of every replica (replica-major, the same number per replica)."""
         if not self.pass_replica:
@@ -231,15 +222,6 @@ class ReplicaEnsemble:
             idx = torch.arange(self.R, dtype=torch.int32, device=theta.device).repeat_interleave(per)
             self._rep_idx[per] = idx
         return self.log_prob_fn(theta, idx)
-
-    def _pick_move(self) -> str:
-        u = uniform01_scalar(stream_key(self.seed, self.step_count, 0, _MOVE_STREAM), 0)
-        acc = 0.0
-        for name, wt in self.moves:
-            acc += wt
-            if u < acc:
-                return name
-        return self.moves[-1][0]
 
     @property
     def cold(self):
@@ -272,54 +254,9 @@ class ReplicaEnsemble:
         self.step_count += 1
         self._n_steps += 1
 
-    def run(self, n_steps: int):
-        for _ in range(n_steps):
-            self.step()
-        return self
-
-    def run_mcmc(self, nsteps: int, thin_by: int = 1):
-        """emcee's ``run_mcmc``: nsteps * thin_by steps, every thin_by-th end-of-step state stored on the device.  The chain is
-        [n, R, w, ndim]: the memory layout of an emcee chain of R w walkers."""
-        nsteps, thin_by = int(nsteps), int(thin_by)
-        if nsteps < 0 or thin_by < 1:
-            raise ValueError("run_mcmc needs nsteps >= 0 and thin_by >= 1")
-        need = self._iteration + nsteps
-        if need > self._chain.shape[0]:
-            chain = torch.empty((need,) + tuple(self._chain.shape[1:]), dtype=torch.float64, device=self.x.device)
-            logp = torch.empty((need,) + tuple(self._chain_logp.shape[1:]), dtype=torch.float64, device=self.x.device)
-            chain[: self._iteration] = self._chain[: self._iteration]
-            logp[: self._iteration] = self._chain_logp[: self._iteration]
-            self._chain, self._chain_logp = chain, logp
-        native = isinstance(self.impl, NativeReplicaMoves)
-        chain_ptr, logp_ptr, acc_ptr = self._chain.data_ptr(), self._chain_logp.data_ptr(), self._walker_acc.data_ptr()
-        chain_row = self._chain.stride(0) * self._chain.element_size()
-        logp_row = self._chain_logp.stride(0) * self._chain_logp.element_size()
-        for i in range(nsteps * thin_by):
-            store = (i + 1) % thin_by == 0
-            slot = self._iteration
-            if native:
-                self._step((chain_ptr + slot * chain_row, logp_ptr + slot * logp_row, acc_ptr) if store else (None, None, acc_ptr))
-            else:
-                self._step(None)
-                if store:
-                    self._chain[slot].copy_(self.x)
-                    self._chain_logp[slot].copy_(self.logp.reshape(self.R, self.w))
-            self._mcmc_steps += 1
-            if store:
-                self._iteration += 1
-        return self
-
-    @property
-    def iteration(self) -> int:
-        return self._iteration
-
     # ---- results ----------------------------------------------------------------------------------------------------
     def _stored(self, v: torch.Tensor, discard: int, thin: int, flat: bool, replica) -> torch.Tensor:
-        if self._iteration == 0:
-            raise AttributeError("you must run the sampler with run_mcmc before accessing the results")
-        if discard < 0 or thin < 1:
-            raise ValueError("get_chain needs discard >= 0 and thin >= 1")
-        v = v[discard + thin - 1: self._iteration: thin]
+        v = self._stored_steps(v, discard, thin)
         if replica is not None:
             if not 0 <= int(replica) < self.R:
                 raise ValueError(f"replica must be in 0..{self.R - 1}")

@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .chain_stats import _on_device
+from ._args import on_device, stream_of
 
 MAX_NDIM = _lib.CF_KDE_MAX_NDIM
 
@@ -215,7 +215,7 @@ def _kernel_sums(y: torch.Tensor, w: Optional[torch.Tensor], q: torch.Tensor, se
         sq = torch.empty(m, dtype=torch.float64, device=y.device) if want_sq else None
         L.check(lib.cf_kde_sum_device(y.data_ptr(), None if w is None else w.data_ptr(), n, d, q.data_ptr(), m, int(self_offset),
                                       out.data_ptr(), None if sq is None else sq.data_ptr(),
-                                      torch.cuda.current_stream(y.device).cuda_stream))
+                                      stream_of(y.device)))
     return out, sq
 
 
@@ -248,7 +248,7 @@ def kde_density(samples, at, weights=None, bandwidth="silverman", leave_one_out:
             raise ValueError(f"kde_density takes the evaluation points as a float64 tensor [m, {d}]")
         if at.device != x.device:
             raise ValueError("kde_density: the evaluation points must be on the device of the samples")
-    x = _on_device(x, "kde_density").contiguous()
+    x = on_device(x, "kde_density").contiguous()
     fit = _Fit(x, w, bw)
     y = fit.whiten(x)
     if leave_one_out:
@@ -300,7 +300,7 @@ def kde_shift(diff, weights=None, bandwidth="silverman", at=None) -> ShiftResult
         at_host = np.asarray(at.detach().cpu().numpy() if isinstance(at, torch.Tensor) else at, dtype=np.float64).reshape(-1)
         if at_host.shape != (d,) or not np.isfinite(at_host).all():
             raise ValueError(f"kde_shift: `at` must be a finite point of {d} coordinates")
-    x = _on_device(x, "kde_shift").contiguous()
+    x = on_device(x, "kde_shift").contiguous()
     fit = _Fit(x, w, bw)
     y = fit.whiten(x)
     q0 = torch.from_numpy(((at_host - fit.mean) @ fit.inv_chol.T).reshape(1, d)).to(x.device)

@@ -267,7 +267,7 @@ def test_host_pointers_beyond_one_piece_have_the_bits_of_the_device_path(pkg, I)
     eng = lk.engine
     try:
         theta = RS.sn_thetas(pkg, S)
-        dacc = I._Acc(n, thr.size, DEV)
+        dacc = I.F.DatumAcc(n, thr.size, DEV)
         dev = I._launch(eng, torch.from_numpy(theta).to(DEV), None, "sn", ("g",), True, thr, dacc, None)
         out, arrs = IS.host_out(L, S, n, want=("g", "sample"))
         hacc, harrs = RS.host_acc(L, n, thr.size)

@@ -246,7 +246,7 @@ def _fake_rows(engine, theta, block="sn", want=I.WANT):
 
 @pytest.fixture
 def host_rows(monkeypatch):
-    monkeypatch.setattr(I.F.chain_stats, "_on_device", lambda x, what: x)
+    monkeypatch.setattr(I.F._args, "on_device", lambda x, what: x)
     monkeypatch.setattr(I, "_to_device", lambda a: torch.from_numpy(np.ascontiguousarray(a)))
     monkeypatch.setattr(I, "rows", _fake_rows)
 

@@ -181,7 +181,7 @@ def _fake_sample_stats(engine, samples, block="sn"):
 
 @pytest.fixture
 def host_reductions(monkeypatch):
-    monkeypatch.setattr(F.chain_stats, "_on_device", lambda x, what: x)
+    monkeypatch.setattr(F._args, "on_device", lambda x, what: x)
     monkeypatch.setattr(F, "_percentile", _host_percentile)
     monkeypatch.setattr(F, "_weighted_quantile", _host_weighted_quantile)
     monkeypatch.setattr(F, "sample_stats", _fake_sample_stats)

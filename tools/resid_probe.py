@@ -89,7 +89,7 @@ def main():
 
     def call(want_a, want_b):
         L.check(lib.cf_resid_device(eng._h, xc.data_ptr(), m, None, L.CF_RB_SN, thr.ctypes.data_as(C.c_void_p), 2,
-                                    sample.data_ptr() if want_a else None, blocks.data_ptr(), C.byref(acc._c) if want_b else None,
+                                    sample.data_ptr() if want_a else None, blocks.data_ptr(), C.byref(acc.c) if want_b else None,
                                     stream))
 
     out = {"probe": "resid_probe", "n_sn": a.n_sn, "rows": a.rows, "chunk_rows": m, "reps": a.reps, "info": eng.info()["gcn_arch"]}
