@@ -210,6 +210,8 @@ class cf_infl_out(C.Structure):
 
 
 CF_CSCALE_MAX_S, CF_CSCALE_CHUNK = 16, 4096
+CF_MARG_MAX_M, CF_MARG_CHUNK, CF_MARG_SLICE = 16, 4096, 256
+CF_MARG_PROFILE, CF_MARG_MARGINAL = 0, 1
 
 
 CF_BRIDGE_MAX_NDIM, CF_BRIDGE_SLICE, CF_BRIDGE_RESULT_DOUBLES = 16, 2048, 8
@@ -351,6 +353,17 @@ EXPORTS = {
     "cf_cscale_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I64, _I32, _VP, _VP, _I32, _I64, _I32, _VP, _VP]),
     "cf_cscale_set_chunk": (C.c_int, [_VP, _I64]),
     "cf_selftest_cscale_host": (C.c_int, [_VP, _VP, _I64, _VP, _I32, _VP, _VP]),
+    "cf_marg_create": (C.c_int, [_VP, _VP, _VP, _I64, _I32, C.c_double, C.c_double, _I32, C.POINTER(_VP)]),
+    "cf_marg_destroy": (None, [_VP]),
+    "cf_marg_info": (C.c_int, [_VP, C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double)]),
+    "cf_marg_apply_device": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP]),
+    "cf_marg_eval_device": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "cf_marg_eval": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP, _VP]),
+    "cf_marg_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I64, _I32, _VP, _I64, _I32, _I32, _VP, _VP]),
+    "cf_marg_set_chunk": (C.c_int, [_VP, _I64]),
+    "cf_selftest_marg_host": (C.c_int, [_VP, _I32, _VP, _VP, _I32, _VP, C.c_double, C.c_double, C.c_double, _I32, _I32, _VP, _VP,
+                                        _VP, _VP]),
     "cf_bridge_forward": (C.c_int, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cf_bridge_points": (C.c_int, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
     "cf_bridge_draw": (C.c_int, [C.c_uint64, _I64, _I64, _I32, _VP, _VP]),

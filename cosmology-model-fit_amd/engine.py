@@ -251,6 +251,7 @@ class LikelihoodEngine:
         self.n_sn = int(d.n_sn)
         self.model_info = model_info(ndim=ndim, params=params, ez_model=ez_model, fde=fde, om_mode=om_mode, n_grid=n_grid, bao=bao,
                                      cmb=cmb, quasar=quasar, devices=devices)
+        self.sampled_slots = {name for name, p in params.items() if p.idx >= 0}  # the slots read from theta (nuisance.py)
         self._h = C.c_void_p()
         self._cf_eval = lib.cf_eval
         self.n_qsr = 0

@@ -1273,6 +1273,73 @@ int cf_cscale_set_chunk(cf_handle* h, int64_t rows);
 int cf_selftest_cscale_host(const double* y, const double* lambda, int64_t n, const double* s, int32_t n_s, double* quad,
                             double* logdet);
 
+/* ---- Linear SN nuisance parameters in closed form (csrc/cosmofit_marg.hip; the driver is
+ * cosmology-model-fit_amd/nuisance.py) -----------------------------------------------------------------------------------------
+ * SN residual r(theta, alpha) = r0(theta) - A alpha: r0 is the handle's own residual row (the marginalised slots fixed in its
+ * descriptor), A [n, m] constant templates (a column of ones: the absolute magnitude; a 0/1 mask: a per-survey offset;
+ * sn_lin_coef: the bulk-flow amplitude), 1 <= m <= CF_MARG_MAX_M, and on alpha_j a prior N(mu_j, sigma_j) or a flat one.  With
+ * P = diag(1 / sigma_j^2) (0 where flat), K = C^-1 A, F = A^T K + P = L_F L_F^T, all formed once on the host (nuisance.project):
+ *   Wt = K L_F^-T [n, m],  ct = L_F^-1 P mu [m],  U = L_F^T [m, m],  pmu = mu^T P mu
+ *   t = Wt^T r0 + ct,   q = sum_j t_j^2 (ascending j),   alpha = U^-1 (t + xi)   (xi = 0: the conditional mean alpha_hat;
+ *   xi ~ N(0, I): a draw from p(alpha | theta, data), whose covariance is F^-1)
+ *   CF_OUT_CHI2:               chi2_prof = (e + pmu) - q, the minimum over alpha with the prior penalty, in both modes
+ *   CF_OUT_LOGL / CF_OUT_LOGP:  (e + 0.5 q) - 0.5 pmu, and + log_norm in mode CF_MARG_MARGINAL (the integral over alpha)
+ * where e is the handle's own value of that kind.  e = -inf stays -inf and a NaN e gives NaN; in both cases the row of alpha is
+ * NaN, whatever the workspace holds.  A row whose projection t is not finite (a NaN or an inf among its residuals) has NaN in t,
+ * q, alpha and the value.
+ *
+ * cf_marg: Wt (zero-padded to 16 columns), ct and U on one device.  cf_marg_create reads Wt [n * m, row-major], ct [m] and the
+ * upper triangle of U [m * m, row-major].  CF_ERR_INVALID: a null argument, n < 1 or > 32768, m outside 1 .. CF_MARG_MAX_M, a
+ * non-finite entry, pmu or log_norm, a diagonal entry of U that is not > 0; CF_ERR_NO_DEVICE without a device.  cf_marg_info
+ * reports what the object holds (any pointer may be NULL).
+ *
+ * cf_marg_apply_device: the kernels alone, on caller-supplied rows d_rows [S rows, pitch >= n]: d_t [S * m], d_q [S], d_alpha
+ * [S * m] (any may be NULL, not all); d_xi [S * m] or NULL.  Columns >= n and rows >= S are never read: a select, not a product
+ * with zero.  CF_ERR_INVALID: a null cf_marg, S < 0 or > 2^31 - 1, pitch < n, no output at all, (S > 0) null rows.
+ *
+ * cf_marg_eval_device: for every row of d_theta [S * ndim] the residual row of the accessor path (chunks of at most
+ * CF_MARG_CHUNK rows into the handle's workspace, as cf_mock_eval_device), then the product T = R Wt on FP64 matrix cores (a wave
+ * owns 16 rows and one slice of CF_MARG_SLICE columns; the slice partials are summed in ascending order) and the row kernel.
+ * d_out [S] and d_alpha [S * m]: either may be NULL, not both.  d_xi [S * m] or NULL.
+ * Determinism: a row's outputs depend on its theta (its residual row), its xi and the cf_marg only -- not on S, the row's
+ * position, the chunking (cf_marg_set_chunk), device or host pointers, the stream, repetition or which outputs are asked for.
+ * Checks, all before the first HIP call (cf_marg_check_args states them without a handle), all CF_ERR_INVALID: a quasar handle,
+ * a handle over several devices, no SN block, a null cf_marg, a cf_marg whose n is not n_sn or that lives on another device, a
+ * bad out_kind or mode, S < 0 or > 2^31 - 1, no output at all, (S > 0) a null d_theta.  S = 0 is a no-op.
+ * Stream contract: that of cf_resid_device (the handle's ONE workspace); a cf_marg has ONE scratch for the slice partials, so a
+ * call on another stream than the previous call on the same cf_marg first waits, on the host, for the device.
+ * cf_marg_eval: the same on host buffers, synchronous, same bits. */
+#define CF_MARG_MAX_M 16
+#define CF_MARG_CHUNK 4096
+#define CF_MARG_SLICE 256
+#define CF_MARG_PROFILE 0
+#define CF_MARG_MARGINAL 1
+typedef struct cf_marg cf_marg;
+int cf_marg_create(const double* Wt, const double* ct, const double* U, int64_t n, int32_t m, double pmu, double log_norm,
+                   int32_t device, cf_marg** out);
+void cf_marg_destroy(cf_marg* p);
+int cf_marg_info(const cf_marg* p, int64_t* n, int32_t* m, int32_t* device, double* pmu, double* log_norm);
+int cf_marg_apply_device(cf_marg* p, const double* d_rows, int64_t pitch, int64_t S, const double* d_xi, double* d_t, double* d_q,
+                         double* d_alpha, void* hip_stream);
+int cf_marg_eval_device(cf_handle* h, cf_marg* p, const double* d_theta, int64_t S, int32_t out_kind, int32_t mode,
+                        const double* d_xi, double* d_out, double* d_alpha, void* hip_stream);
+int cf_marg_eval(cf_handle* h, cf_marg* p, const double* theta, int64_t S, int32_t out_kind, int32_t mode, const double* xi,
+                 double* out, double* alpha);
+/* The argument rules above as host arithmetic on the facts of a handle (its n_sn, whether it is a quasar handle, its number of
+ * devices, its device) and of a cf_marg (has_marg: non-null; its n and device).  No handle and no device needed. */
+int cf_marg_check_args(int64_t n_sn, int32_t is_quasar, int32_t n_devices, int32_t handle_device, int32_t has_marg, int64_t marg_n,
+                       int32_t marg_device, const void* theta, int64_t S, int32_t out_kind, int32_t mode, const void* out,
+                       const void* alpha);
+/* Rows per chunk of the following cf_marg_eval_device / cf_marg_eval calls of this handle, 1 .. 65536; 0 restores
+ * CF_MARG_CHUNK.  The results do not depend on it: it exists so that tests can cross chunk boundaries with few rows. */
+int cf_marg_set_chunk(cf_handle* h, int64_t rows);
+/* The arithmetic of the row kernel compiled for the host, in the same order of operations (one __host__ __device__ function per
+ * step, shared with the kernel): from one row's slice partials part [n_slice * 16] (entry b * 16 + j: slice b, component j),
+ * t [m], q, alpha [m] and the value of (out_kind, mode) for the engine value e (any output may be NULL).  No device needed. */
+int cf_selftest_marg_host(const double* part, int32_t n_slice, const double* ct, const double* U, int32_t m, const double* xi,
+                          double pmu, double log_norm, double e, int32_t out_kind, int32_t mode, double* t, double* q,
+                          double* alpha, double* value);
+
 /* ---- Bridge-sampling evidence (csrc/cosmofit_bridge.hip; the driver is cosmology-model-fit_amd/evidence.py) ----------------
  * ln Z of a posterior in a finite box from a chain and draws of a Gaussian fitted to it in unbounded coordinates (Meng & Wong
  * 1996; Gronau et al. 2017).  Everything is float64, row-major, device pointers on the current device, asynchronous on
