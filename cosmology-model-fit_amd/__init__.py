@@ -15,8 +15,8 @@ from . import cmb_data, interpolator, laplace, likelihoods, quasars, scripts, so
 
 
 def __getattr__(name):
-    # `ensemble`, `chain_stats`, `marginals`, `nested`, `optimize`, `derived`, `gp`, `quintessence`, `fit_report`, `mocks`, `tension`, `influence`, `evidence`, `leaveout`, `replicas`, `covscale` and `nuisance` need torch; import them lazily so that ctypes-only users do not pay for it
-    if name in ("ensemble", "chain_stats", "marginals", "nested", "optimize", "derived", "gp", "quintessence", "fit_report", "mocks", "tension", "influence", "evidence", "leaveout", "replicas", "covscale", "nuisance"):
+    # `ensemble`, `chain_stats`, `marginals`, `nested`, `optimize`, `derived`, `gp`, `quintessence`, `fit_report`, `mocks`, `tension`, `influence`, `evidence`, `leaveout`, `replicas`, `covscale`, `nuisance` and `scan` need torch; import them lazily so that ctypes-only users do not pay for it
+    if name in ("ensemble", "chain_stats", "marginals", "nested", "optimize", "derived", "gp", "quintessence", "fit_report", "mocks", "tension", "influence", "evidence", "leaveout", "replicas", "covscale", "nuisance", "scan"):
         import importlib
         return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)

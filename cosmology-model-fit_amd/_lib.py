@@ -212,6 +212,7 @@ class cf_infl_out(C.Structure):
 CF_CSCALE_MAX_S, CF_CSCALE_CHUNK = 16, 4096
 CF_MARG_MAX_M, CF_MARG_CHUNK, CF_MARG_SLICE = 16, 4096, 256
 CF_MARG_PROFILE, CF_MARG_MARGINAL = 0, 1
+CF_SCAN_CHUNK, CF_SCAN_TILE, CF_SCAN_MAX_K = 4096, 64, (1 << 24) - 1
 
 
 CF_BRIDGE_MAX_NDIM, CF_BRIDGE_SLICE, CF_BRIDGE_RESULT_DOUBLES = 16, 2048, 8
@@ -364,6 +365,15 @@ EXPORTS = {
     "cf_marg_set_chunk": (C.c_int, [_VP, _I64]),
     "cf_selftest_marg_host": (C.c_int, [_VP, _I32, _VP, _VP, _I32, _VP, C.c_double, C.c_double, C.c_double, _I32, _I32, _VP, _VP,
                                         _VP, _VP]),
+    "cf_scan_create": (C.c_int, [_VP, _I64, _I64, _I64, _VP, _I32, C.POINTER(_VP)]),
+    "cf_scan_destroy": (None, [_VP]),
+    "cf_scan_info": (C.c_int, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I64)]),
+    "cf_scan_apply_device": (C.c_int, [_VP, _VP, _I64, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "cf_scan_eval_device": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "cf_scan_eval": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "cf_scan_check_args": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _I64, _I64, _I32, _VP, _I64, _I32, _I32, _VP, _I64]),
+    "cf_scan_set_chunk": (C.c_int, [_VP, _I64]),
+    "cf_selftest_scan_host": (C.c_int, [_VP, _I64, _I64, _I64, _VP, _I32, _VP, _VP, _VP, _VP, _VP]),
     "cf_bridge_forward": (C.c_int, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cf_bridge_points": (C.c_int, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
     "cf_bridge_draw": (C.c_int, [C.c_uint64, _I64, _I64, _I32, _VP, _VP]),

@@ -142,6 +142,7 @@ struct cf_handle {
   int64_t infl_chunk = 0;
   int64_t cscale_chunk = 0;  // rows per chunk of cf_cscale_eval_device (0: CF_CSCALE_CHUNK); residual rows and chi^2 shares are the fit report's
   int64_t marg_chunk = 0;  // rows per chunk of cf_marg_eval_device (0: CF_MARG_CHUNK); it shares the fit report's chunk buffers
+  int64_t scan_chunk = 0;  // rows per chunk of cf_scan_eval_device (0: CF_SCAN_CHUNK); it shares the fit report's chunk buffers
 };
 
 // An entry point's hold on its handle: h->mu locked and the handle's device current (cf_host.h: DeviceScope) until it returns.

@@ -1456,6 +1456,71 @@ int cf_reweight_check_args(const void* d_lw, int64_t lw_pitch, int64_t S, int32_
 int cf_reweight_device(const double* d_lw, int64_t lw_pitch, int64_t S, int32_t G, const double* d_w0, const double* d_x,
                        int64_t x_pitch, int32_t ncol, const double* pivot, double* d_out, void* hip_stream);
 
+/* ---- Template scans (csrc/cosmofit_scan.hip; the driver is cosmology-model-fit_amd/scan.py) ---------------------------------
+ * K candidate templates a_k on top of a base model A0 [n, m0] of the SN residual.  With K' the SN precision matrix deflated by
+ * the base (K' = C^-1 - Wt Wt^T, Wt of nuisance.project), g_k = K' a_k, F_k = a_k^T g_k + 1 / sigma_k^2 and
+ * v_k = g_k / sqrt(F_k), all formed once on the host (scan.prepare), a residual row r0 gives
+ *   s_k = v_k^T r0                     the signed z-score of candidate k given the base
+ *   dchi2_k = s_k^2                    what fitting a_k as well would take off the profiled chi^2
+ *   statistic: s^2 (sign 0), max(s, 0)^2 (sign +1), max(-s, 0)^2 (sign -1)
+ * cf_scan: V [n, K] (column k: v_k) and the live flags on one device.  cf_scan_create reads V [n rows at pitch ld >= K] and
+ * live [K] (NULL: all live); the column of a candidate that is not live is stored as zero, so its score is exactly 0.0, and it
+ * never wins a row.  V is zero-padded to multiples of the kernel's tile in both directions.  CF_ERR_INVALID: a null argument,
+ * n outside 1 .. 32768, K outside 1 .. 2^24 - 1, ld < K, a non-finite entry; CF_ERR_NO_DEVICE without a device.  cf_scan_info
+ * reports n, K, the device and the number of live candidates (any pointer may be NULL).
+ *
+ * cf_scan_apply_device: the kernels alone on caller-supplied rows d_rows [S rows, pitch >= n]; columns >= n and rows >= S are
+ * never read (a select, not a product with zero).  Z = R V on FP64 matrix cores (one accumulator per output, ascending k loop, no
+ * split-k, no atomics) with the reductions fused behind it, so Z reaches memory only when d_map is given.  Outputs, any may be
+ * NULL, not all:
+ *   d_best [S], d_best_k [S] (int32), d_s_best [S]: the largest statistic of the row over the live candidates, its candidate
+ *     (ties: the smallest k) and the signed score there; a row with a score that is not finite has NaN, -1, NaN, as has a row of
+ *     an object without a live candidate;
+ *   d_map [S rows at map_pitch >= K]: the scores s_k;
+ *   d_colacc [2 K + 1]: RUNNING accumulators the call adds to: (sum w s_k, sum w s_k^2) at 2 k, 2 k + 1 and sum w at 2 K, with
+ *     w = d_w [S] (NULL: ones).  Blocks of CF_SCAN_TILE rows are summed in ascending order from 0.0, then added in ascending order.
+ * Determinism: the score of (row, k) depends on that row's residuals and column k of V only -- not on S, the row's position, the
+ * chunking, the stream, the pointer kind, sign, which outputs are asked for or which other candidates there are; best is the
+ * maximum of the statistics of the scores d_map would hold.  The accumulators have the same bits for the same cut of a chain into
+ * calls (and chunks) and differ by rounding across cuts.
+ * CF_ERR_INVALID: a null cf_scan, S < 0 or > 2^31 - 1, pitch < n, sign outside -1 .. 1, no output at all, map_pitch < K with a
+ * map, (S > 0) null rows.
+ *
+ * cf_scan_eval_device: for every row of d_theta [S * ndim] the residual row of the accessor path (chunks of at most
+ * CF_SCAN_CHUNK rows into the handle's workspace, as cf_marg_eval_device), the handle's own chi^2 to d_chi2 [S] (may be NULL) and
+ * the kernels above behind it on the same stream.  Checks, all before the first HIP call (cf_scan_check_args states them without
+ * a handle: n_outputs counts the non-null outputs, d_chi2 included), all CF_ERR_INVALID: a quasar handle, a handle over several
+ * devices, no SN block, a null cf_scan, a cf_scan whose n is not n_sn or that lives on another device, a bad sign, S out of
+ * range, no output, a map pitch below K, (S > 0) a null d_theta.  S = 0 is a no-op.  Stream contract: that of
+ * cf_marg_eval_device; a cf_scan has ONE scratch, so a call on another stream than the previous call on the same cf_scan first
+ * waits, on the host, for the device.  cf_scan_eval: the same on host buffers, synchronous, same bits (colacc is read and
+ * written). */
+#define CF_SCAN_CHUNK 4096
+#define CF_SCAN_TILE 64
+#define CF_SCAN_MAX_K (((int64_t)1 << 24) - 1)
+typedef struct cf_scan cf_scan;
+int cf_scan_create(const double* V, int64_t n, int64_t K, int64_t ld, const uint8_t* live, int32_t device, cf_scan** out);
+void cf_scan_destroy(cf_scan* p);
+int cf_scan_info(const cf_scan* p, int64_t* n, int64_t* K, int32_t* device, int64_t* n_live);
+int cf_scan_apply_device(cf_scan* p, const double* d_rows, int64_t pitch, int64_t S, int32_t sign, const double* d_w, double* d_best,
+                         int32_t* d_best_k, double* d_s_best, double* d_map, int64_t map_pitch, double* d_colacc, void* hip_stream);
+int cf_scan_eval_device(cf_handle* h, cf_scan* p, const double* d_theta, int64_t S, int32_t sign, const double* d_w, double* d_chi2,
+                        double* d_best, int32_t* d_best_k, double* d_s_best, double* d_map, int64_t map_pitch, double* d_colacc,
+                        void* hip_stream);
+int cf_scan_eval(cf_handle* h, cf_scan* p, const double* theta, int64_t S, int32_t sign, const double* w, double* chi2, double* best,
+                 int32_t* best_k, double* s_best, double* map, int64_t map_pitch, double* colacc);
+int cf_scan_check_args(int64_t n_sn, int32_t is_quasar, int32_t n_devices, int32_t handle_device, int32_t has_scan, int64_t scan_n,
+                       int64_t scan_K, int32_t scan_device, const void* theta, int64_t S, int32_t sign, int32_t n_outputs,
+                       const void* map, int64_t map_pitch);
+/* Rows per chunk of the following cf_scan_eval_device / cf_scan_eval calls of this handle, 1 .. 65536; 0 restores CF_SCAN_CHUNK.
+ * No score or row output depends on it; the column accumulators depend on it by rounding only. */
+int cf_scan_set_chunk(cf_handle* h, int64_t rows);
+/* The two reductions compiled for the host from a given map [S rows at pitch >= K] (the steps are __host__ __device__ functions
+ * shared with the kernels: the statistic of a score, the comparison with its tie rule, a row's step of a block's column sums):
+ * best, best_k, s_best [S] and colacc [2 K + 1] (read and written); any output may be NULL; live [K] or NULL.  No device needed. */
+int cf_selftest_scan_host(const double* map, int64_t S, int64_t K, int64_t pitch, const uint8_t* live, int32_t sign, const double* w,
+                          double* best, int32_t* best_k, double* s_best, double* colacc);
+
 #ifdef __cplusplus
 }
 #endif
